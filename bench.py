@@ -17,6 +17,11 @@ itself under torch.distributed.run with N ranks on 127.0.0.1.  Every rank render
 of the 8-camera ring (view-parallel, weak scaling) and the per-Gaussian parameter gradients are
 summed across ranks over RCCL every step -- the exchange step north_star names.
 
+A plain run sets up, warms up, times --steps steps and prints the result line; --full adds every other
+measurement after the timed region (per-stage timers and roofline, fixed camera, tight binning, API path, the
+reference on this GPU, the skewed scene, the C2 / C4 configs, exchange timing and 8-GPU prediction, CPU baselines).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -39,8 +44,18 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: per-stage timers and the roofline of the dominant kernel, "
+                         "the informative passes after the timed region (fixed camera, tight binning, API path, reference on this "
+                         "GPU, skewed scene, the C2 / C4 configs), the exchange timing and the 8-GPU prediction of N > 1 runs, the "
+                         "PMC figures and the CPU baselines (each still subject to its --no-* option).  Off: set-up, warm-up, the "
+                         "timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; the "
+                         "rendered image whole, the per-Gaussian outputs -- radii and the gradients -- on a fixed seeded sample "
+                         "of at most %d rows, whose indices are DIR/rows.npy in float64)" % DUMP_ROWS)
     ap.add_argument("--spinup-steps", type=int, default=100,
                     help="untimed steps before the W warm-up steps: the process spends seconds on the host building the "
                          "scene, the idle GPU drops its clocks, and a short warm-up can end before they are back up")
@@ -52,12 +67,12 @@ def parse_args():
     ap.add_argument("--points", type=int, default=0, help="override the number of Gaussians (debug only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the informative passes after the timed region (tight binning, API path, reference on this GPU, "
+                    help="with --full: skip the informative passes after the timed region (tight binning, API path, reference on this GPU, "
                          "skewed scene); used under rocprofv3 so that per-kernel averages are those of the headline mode only")
     ap.add_argument("--exact", action="store_true", help="use the EXACT blend arithmetic")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="frg_set_option(NAME, VALUE) before anything runs (tuning experiments; repeatable)")
-    ap.add_argument("--no-stage-timers", action="store_true", help="do not record per-stage hipEvents (no roofline object)")
+    ap.add_argument("--no-stage-timers", action="store_true", help="with --full: do not record per-stage hipEvents (no roofline object)")
     ap.add_argument("--keep-for-backward", action="store_true",
                     help="C2 (forward only): the plain forward, which leaves checkpoints and work items for a backward, instead of "
                          "frg_forward_args::forward_only (A/B)")
@@ -120,7 +135,10 @@ def parse_args():
     ap.add_argument("--densify-stats", action="store_true",
                     help="N>1: also all-reduce the densification statistics of vanilla 3DGS every step (radii MAX, "
                          "viewspace-gradient norm and visibility count SUM; gaussian_model.py:404-407)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch_if_needed(args):
@@ -215,6 +233,35 @@ def dry_run_plumbing(args, world, rank):
                                      "exchange": "slotsum", "chunks": len(ex.chunks), "capacity_rows": list(ex.capacity),
                                      "repacks": ex.stats["repacks"], "parallelism": f"view-parallel x{world}"}}))
     dist.destroy_process_group()
+
+
+DUMP_ROWS = 65536              # --dump-outputs: per-Gaussian outputs on a fixed seeded sample of this many rows (all rows below it)
+DUMP_SEED = 20241022
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, image, per_gaussian: dict, P: int):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as float32 .npy files.  The image is
+    written whole, every per-Gaussian array ([P, ...]) on the same rows: all of them when P <= DUMP_ROWS, else a fixed
+    seeded sample (the same for every run at the same P) whose indices are rows.npy (float64).  Radii are integers below
+    2^24: exact in float32."""
+    import numpy as np
+    import torch
+    if P > DUMP_ROWS:
+        rows = torch.randperm(P, generator=torch.Generator().manual_seed(DUMP_SEED))[:DUMP_ROWS].sort().values
+    else:
+        rows = torch.arange(P)
+    arrays = {"image": image.detach().float().cpu().numpy(), "rows": rows.numpy().astype(np.float64)}
+    for name, t in per_gaussian.items():
+        arrays[name] = t.detach()[rows.to(t.device)].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes would exceed the limit of {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays), "bytes": total, "rows_sampled": int(rows.numel()),
+            "note": "the last timed step's image (whole) and per-Gaussian outputs (the rows in rows.npy), float32"}
 
 
 def stage_bytes(P, V, R, N, T):
@@ -503,7 +550,10 @@ def main():
     if args.gpus != world and rank == 0:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}: reporting n_gpus={world}", file=sys.stderr)
 
-    extras = not (args.no_extras or args.no_tight_pass)
+    # a plain run does what its headline figure needs; --full adds every other measurement and check
+    full = args.full
+    extras = full and not (args.no_extras or args.no_tight_pass)
+    timers = full and not args.no_stage_timers
     cfg = scenes.CONFIGS[args.config]
     P = args.points or cfg["P"]
     shell = None
@@ -521,7 +571,7 @@ def main():
         if _lib.set_option(k, int(v)) < 0 and "unknown option" in _lib.last_error():
             raise SystemExit(f"--option {kv}: {_lib.last_error()}")
     _lib.set_option("exact_blend", 1 if args.exact else 0)
-    _lib.set_option("profile", 0 if args.no_stage_timers else 1)
+    _lib.set_option("profile", 1 if timers else 0)
     _lib.set_option("tight_binning", 1 if args.tight_binning else 0)
     scene_d = scene.to(dev)
     reduce_probe = None
@@ -643,7 +693,6 @@ def main():
         dt = time.perf_counter() - t0
         return dt, [evs[i].elapsed_time(evs[i + 1]) for i in range(nsteps)]
 
-    timers = not args.no_stage_timers
     # N > 1: the first steps of a plan are a TRIAL -- the slot-sum path's multi-rank collectives have only ever run on one GPU
     # (single-rank RCCL, two ranks sharing a GPU over gloo).  A rank on which they raise tells the others (one MAX all-reduce),
     # and every rank falls back to the next plan down: slotsum -> factored -> allreduce.  (A collective that HANGS cannot be
@@ -713,6 +762,18 @@ def main():
     if dist:
         dist.barrier()
     timed_views = [view_ids[i % n_views] for i in range(args.steps)]
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, before anything below renders again
+        per = {"radii": vpr.radii}
+        if do_backward:
+            g = vpr.exchanges[(args.steps - 1) % 2 if schedule[0] == "stale" else 0].views
+            per.update(dL_dmeans3D=g["means3D"], dL_dsh=g["shs"], dL_dopacity=g["opacities"], dL_dscales=g["scales"],
+                       dL_drotations=g["rotations"])
+            if not exchanging:     # the own view's rank-local outputs (with an exchange they are not the step's result)
+                per.update(dL_dmeans2D=vpr.dL_dmeans2D, dL_dcolors=vpr.dL_dcolors, dL_dcov3D=vpr.dL_dcov3D)
+        outputs = dump_outputs(args.dump_outputs, vpr.out_color, per, P)
+        outputs["view"] = timed_views[-1]
     stage_avg, dom_ms = {}, None
     if timers:
         # hipEvents recorded by the C ABI on the launch stream around the dominant kernel of every
@@ -751,7 +812,7 @@ def main():
         cycle[0] = True
     cycle[0] = False        # the passes below compare modes on one camera
     compute_only, other_schedule = None, None
-    if exchanging:
+    if exchanging and full:
         def max_over_ranks(x):
             t_ = torch.tensor([x], dtype=torch.float64, device=dev)
             dist.all_reduce(t_, op=dist.ReduceOp.MAX)
@@ -940,7 +1001,7 @@ def main():
         }
         if shell is not None:
             out["config"]["mesh_triangles"] = int(shell.faces.shape[0])
-        if do_backward and shell is None:
+        if full and do_backward and shell is None:
             # what the view-parallel step is predicted to cost on one 8-GPU node (frosting_amd.parallel.predict_exchange:
             # bytes / nominal xGMI link rate at 80 % efficiency -- arithmetic, not a measurement), for the plan of this run
             # and for the alternatives; render = this run's step without the exchange
@@ -994,7 +1055,9 @@ def main():
         if skew:
             out["skew_scene"] = skew
         out.update(side)
-        whole = pmc_traffic("*", args.config, P)
+        if outputs:
+            out["outputs"] = outputs
+        whole = pmc_traffic("*", args.config, P) if full else None
         if whole == "stale":
             out["op_hbm"]["measured_bytes_per_view"] = "stale"
             out["op_hbm"]["measured_note"] = ("the newest committed PMC passes (profiles/r0N_pmc_traffic.json) were taken with other "
@@ -1004,7 +1067,7 @@ def main():
             out["op_hbm"]["measured_over_algorithmic"] = whole["bytes"] / total_bytes
             out["op_hbm"]["measured_note"] = (f"sum over the stages of the HBM-side bytes per launch from the committed rocprofv3 PMC "
                                               f"passes of this workload ({whole['source']}); below 1: L2 / Infinity-Cache reuse")
-        if not args.no_cpu_baseline and world == 1 and shell is None:
+        if full and not args.no_cpu_baseline and world == 1 and shell is None:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.config, P, do_backward)
             except Exception as ex:  # the baseline is informative; never lose the GPU number over it

@@ -2,11 +2,48 @@
 the same seeded inputs."""
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
 from frosting_amd import scenes
 from frosting_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _C
+
+
+# A committed file stays below 1 MiB: a raster fixture that would not keeps its largest arrays in golden/more/<same name>.
+FIXTURE_LIMIT = 1 << 20
+
+
+def _fixture_rest(path):
+    return os.path.join(os.path.dirname(path), "more", os.path.basename(path))
+
+
+def load_fixture(path) -> dict:
+    """The arrays of tests/golden/<name>.npz, with those kept in golden/more/<name>.npz"""
+    with np.load(path) as f:
+        fx = dict(f)
+    if os.path.exists(_fixture_rest(path)):
+        with np.load(_fixture_rest(path)) as f:
+            fx.update(f)
+    return fx
+
+
+def save_fixture(path, arrays: dict):
+    """np.savez_compressed, the largest arrays moved to golden/more/<name>.npz until the main file fits FIXTURE_LIMIT"""
+    main, rest = dict(arrays), {}
+    while True:
+        np.savez_compressed(path, **main)
+        if os.path.getsize(path) < FIXTURE_LIMIT:
+            break
+        big = max(main, key=lambda k: np.asarray(main[k]).nbytes)
+        rest[big] = main.pop(big)
+    if rest:
+        os.makedirs(os.path.dirname(_fixture_rest(path)), exist_ok=True)
+        np.savez_compressed(_fixture_rest(path), **rest)
+        assert os.path.getsize(_fixture_rest(path)) < FIXTURE_LIMIT, _fixture_rest(path)
+    elif os.path.exists(_fixture_rest(path)):
+        os.remove(_fixture_rest(path))
 
 
 def settings_for(cam, bg, sh_degree, device, scale_modifier=1.0, debug=False):

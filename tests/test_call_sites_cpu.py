@@ -1,47 +1,23 @@
-"""Mechanical "callers unchanged" check (CPU tier): the reference's own call sites of the rasterizer are parsed with
-`ast` and every import, keyword and positional parameter they use must be accepted by the drop-in package.
+"""Mechanical "callers unchanged" check (CPU tier): the reference's own call sites of the rasterizer, parsed with `ast`
+(tools/make_golden_call_sites.py, recorded in tests/golden/call_sites.json) -- every import, keyword and positional
+parameter they use must be accepted by the drop-in package.
 
 Sites: gaussian_splatting/gaussian_renderer/__init__.py:14,85-93,
 frosting_scene/frosting_model.py:29,1452-1467,1649-1657 (and its other render paths),
 frosting_scene/sugar_model.py:10,2213-2228,2317-2325, and the alternative backend that proves the interface's shape,
-gsplat_wrapper/rasterization.py:18-114.  The tree is only present in the build container: skipped elsewhere.
+gsplat_wrapper/rasterization.py:18-114.
 """
 import ast
 import inspect
+import json
 import os
 
 import pytest
 
-REF = os.environ.get("FROSTING_REFERENCE", "/root/reference")
 CALLERS = ["gaussian_splatting/gaussian_renderer/__init__.py", "frosting_scene/frosting_model.py",
            "frosting_scene/sugar_model.py"]
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
-
-
-def _parse(rel):
-    with open(os.path.join(REF, rel)) as f:
-        return ast.parse(f.read(), filename=rel)
-
-
-def _calls(tree, name):
-    """ast.Call nodes whose callee is the bare name `name`"""
-    return [n for n in ast.walk(tree) if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == name]
-
-
-def _rasterizer_calls(tree):
-    """calls of a variable that the SAME function bound to `GaussianRasterizer(...)` (other functions of these files
-    reuse the name `rasterizer` for a mesh rasterizer)"""
-    out = []
-    for fn in ast.walk(tree):
-        if not isinstance(fn, (ast.FunctionDef, ast.AsyncFunctionDef)):
-            continue
-        names = set()
-        for n in ast.walk(fn):
-            if isinstance(n, ast.Assign) and isinstance(n.value, ast.Call) and isinstance(n.value.func, ast.Name) \
-                    and n.value.func.id == "GaussianRasterizer":
-                names |= {t.id for t in n.targets if isinstance(t, ast.Name)}
-        out += [n for n in ast.walk(fn) if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id in names]
-    return out
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "call_sites.json")) as _f:
+    SITES = json.load(_f)
 
 
 def _api():
@@ -65,10 +41,7 @@ def test_imports_of_the_call_sites_resolve(rel):
                 exported |= {e.id for e in ast.walk(t) if isinstance(e, ast.Name)}
         elif isinstance(n, ast.FunctionDef):
             exported.add(n.name)
-    wanted = set()
-    for n in ast.walk(_parse(rel)):
-        if isinstance(n, ast.ImportFrom) and n.module == "diff_gaussian_rasterization":
-            wanted |= {a.name for a in n.names}
+    wanted = set(SITES["callers"][rel]["imports"])
     assert wanted, f"{rel} no longer imports diff_gaussian_rasterization"
     assert wanted <= exported, wanted - exported
 
@@ -76,15 +49,15 @@ def test_imports_of_the_call_sites_resolve(rel):
 @pytest.mark.parametrize("rel", CALLERS)
 def test_settings_keywords_of_the_call_sites(rel):
     Settings, _ = _api()
-    calls = _calls(_parse(rel), "GaussianRasterizationSettings")
+    calls = SITES["callers"][rel]["settings_calls"]
     assert calls, f"{rel}: no GaussianRasterizationSettings(...) call found"
     for c in calls:
-        assert not c.args, f"{rel}:{c.lineno}: positional settings arguments"
-        kws = [k.arg for k in c.keywords]
-        assert None not in kws, f"{rel}:{c.lineno}: **kwargs"
-        assert set(kws) <= set(Settings._fields), (rel, c.lineno, set(kws) - set(Settings._fields))
+        assert not c["positional"], f"{rel}:{c['line']}: positional settings arguments"
+        kws = c["keywords"]
+        assert None not in kws, f"{rel}:{c['line']}: **kwargs"
+        assert set(kws) <= set(Settings._fields), (rel, c["line"], set(kws) - set(Settings._fields))
         # a NamedTuple without defaults: every field must be given, as the reference's is
-        assert set(kws) == set(Settings._fields), (rel, c.lineno, set(Settings._fields) - set(kws))
+        assert set(kws) == set(Settings._fields), (rel, c["line"], set(Settings._fields) - set(kws))
 
 
 @pytest.mark.parametrize("rel", CALLERS)
@@ -94,32 +67,29 @@ def test_rasterizer_call_keywords_of_the_call_sites(rel):
     params = [p for p in sig.parameters.values() if p.name != "self"]
     accepted = {p.name for p in params}
     required = {p.name for p in params if p.default is inspect.Parameter.empty}
-    tree = _parse(rel)
-    ctor = _calls(tree, "GaussianRasterizer")
+    ctor = SITES["callers"][rel]["rasterizer_ctor_calls"]
     assert ctor
     for c in ctor:
-        assert [k.arg for k in c.keywords] == ["raster_settings"] and not c.args, (rel, c.lineno)
+        assert c["keywords"] == ["raster_settings"] and not c["positional"], (rel, c["line"])
     assert "raster_settings" in inspect.signature(Rasterizer.__init__).parameters
-    calls = _rasterizer_calls(tree)
+    calls = SITES["callers"][rel]["rasterizer_calls"]
     assert calls, f"{rel}: no call of a GaussianRasterizer instance found"
     for c in calls:
-        assert not c.args, f"{rel}:{c.lineno}: positional call"
-        kws = {k.arg for k in c.keywords}
-        assert kws <= accepted, (rel, c.lineno, kws - accepted)
-        assert required <= kws, (rel, c.lineno, required - kws)
+        assert not c["positional"], f"{rel}:{c['line']}: positional call"
+        kws = set(c["keywords"])
+        assert kws <= accepted, (rel, c["line"], kws - accepted)
+        assert required <= kws, (rel, c["line"], required - kws)
 
 
 def test_interface_shape_of_the_alternative_backend():
     """gsplat_wrapper/rasterization.py re-implements the same two classes over gsplat: its settings fields and its
     forward parameter list (positional order included) are the interface every caller relies on."""
     Settings, Rasterizer = _api()
-    tree = _parse("gsplat_wrapper/rasterization.py")
-    classes = {n.name: n for n in ast.walk(tree) if isinstance(n, ast.ClassDef)}
-    init = next(f for f in classes["GaussianRasterizationSettings"].body if isinstance(f, ast.FunctionDef) and f.name == "__init__")
-    fields = [a.arg for a in init.args.args if a.arg != "self"]
+    alt = SITES["alternative_backend"]
+    assert alt["file"] == "gsplat_wrapper/rasterization.py"
+    fields = alt["settings_init_fields"]
     assert fields == list(Settings._fields)
-    fwd = next(f for f in classes["GaussianRasterizer"].body if isinstance(f, ast.FunctionDef) and f.name == "forward")
-    theirs = [a.arg for a in fwd.args.args if a.arg != "self"]
+    theirs = alt["forward_params"]
     ours = [p for p in inspect.signature(Rasterizer.forward).parameters if p != "self"]
     assert set(theirs) <= set(ours)
     # the two leading positional parameters agree (means3D, means2D); the rest are passed by keyword everywhere
@@ -129,9 +99,8 @@ def test_interface_shape_of_the_alternative_backend():
 def test_native_module_exports_named_by_the_reference():
     """DGR/ext.cpp:15-18 exports three functions; the autograd wiring above them calls them by these names
     (DGR/diff_gaussian_rasterization/__init__.py:82,130,183)."""
-    src = open(os.path.join(REF, "gaussian_splatting/submodules/diff-gaussian-rasterization/ext.cpp")).read()
     import re
-    names = set(re.findall(r'm\.def\("(\w+)"', src))
+    names = set(SITES["native_exports"]["names"])
     assert names == {"rasterize_gaussians", "rasterize_gaussians_backward", "mark_visible"}
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     binding = open(os.path.join(here, "frosting_amd", "csrc", "torch_ext", "torch_binding.cpp")).read()

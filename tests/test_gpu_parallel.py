@@ -407,7 +407,7 @@ def test_bench_two_ranks_from_a_bare_shell(gpu_device, exchange):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--exchange", exchange,
-                        "--points", "30000", "--steps", "3", "--warmup", "2", "--spinup-steps", "2", "--no-cpu-baseline",
+                        "--points", "30000", "--steps", "3", "--warmup", "2", "--spinup-steps", "2", "--full", "--no-cpu-baseline",
                         "--no-extras", "--probe-exchange"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

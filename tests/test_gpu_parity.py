@@ -74,7 +74,7 @@ def test_native_library_is_loaded(gpu_device):
 @pytest.mark.parametrize("exact", [1, 0])
 @pytest.mark.parametrize("path", RASTER_FIXTURES, ids=[os.path.basename(p) for p in RASTER_FIXTURES])
 def test_against_reference_golden_fixture(gpu_device, path, exact, ops):
-    fx = np.load(path)
+    fx = Hh.load_fixture(path)
     scene, cam, bg = scenes.config_scene(str(fx["cfg"]), int(fx["view"]), P=int(fx["P"]))
     _lib.set_option("exact_blend", exact)
     out, args = Hh.run_ours_native(scene, cam, bg, gpu_device, str(fx["mode"]), str(fx["cov"]), ops=ops)

@@ -30,7 +30,7 @@ def _oracle_for(fx):
 
 @pytest.mark.parametrize("path", RASTER_FIXTURES, ids=[os.path.basename(p) for p in RASTER_FIXTURES])
 def test_oracle_matches_reference_fixture(path):
-    fx = np.load(path)
+    fx = Hh.load_fixture(path)
     scene, cam, bg, st = _oracle_for(fx)
     vis = fx["radii"] > 0
     # integer artefacts: bit-exact

@@ -30,7 +30,7 @@ sparse)
 smoke)
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log; tail -2 $O/smoke.log ;;
 bench)
-  timeout 1200 python bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench_c3.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 2500 $O/bench_c3.json; tail -3 $O/bench.err ;;
+  timeout 1200 python bench.py --steps 20 --warmup 5 --full ${BENCH_ARGS:-} > $O/bench_c3.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 2500 $O/bench_c3.json; tail -3 $O/bench.err ;;
 prof)
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -- python "$ROOTD/bench.py" --steps 16 --warmup 3 --spinup-steps 24 --no-cpu-baseline --no-extras > "$O/prof_bench_c3.json" 2> "$O/prof.err")
   f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/bench_c3_kernel_stats.csv && head -18 $O/bench_c3_kernel_stats.csv | cut -c1-70,150-230
@@ -51,7 +51,7 @@ exchange)
   IFS='|' read -ra EMODES <<< "${EXCHANGE_MODES:---exchange slotsum|--exchange slotsum --chunks 1|--exchange slotsum --chunks 2|--exchange slotsum --chunks 4|--exchange factored|--exchange factored --sync-exchange|--exchange factored --reduce direct|--exchange allreduce|--exchange sparse}"
   for mode in "${EMODES[@]}"; do
     echo "== bench.py --force-exchange $mode" >> $O/exchange_1rank.log
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --force-exchange $mode 2>&1 | grep -v "^Librccl\|^RCCL\|^HIP\|^ROCm\|^Hostname\|amdgpu.ids" | tail -2 >> $O/exchange_1rank.log
+    timeout 300 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras --force-exchange $mode 2>&1 | grep -v "^Librccl\|^RCCL\|^HIP\|^ROCm\|^Hostname\|amdgpu.ids" | tail -2 >> $O/exchange_1rank.log
   done
   grep -c metric $O/exchange_1rank.log ;;
 pmc)
@@ -74,7 +74,7 @@ tworank)
   for ex in ${TWORANK_PLANS:-slotsum factored allreduce}; do
     echo "== $ex" >> $O/two_rank.log
     FRG_BENCH_ONE_GPU=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 \
-      bench.py --gpus 2 --steps 6 --warmup 3 --spinup-steps 2 --backend gloo --exchange $ex --points 400000 --no-cpu-baseline --no-extras 2>&1 | grep -v "amdgpu.ids\|socket.cpp\|^\*\*\*\|OMP_NUM" | tail -4 | cut -c1-900 >> $O/two_rank.log
+      bench.py --gpus 2 --steps 6 --warmup 3 --spinup-steps 2 --backend gloo --exchange $ex --points 400000 --full --no-cpu-baseline --no-extras 2>&1 | grep -v "amdgpu.ids\|socket.cpp\|^\*\*\*\|OMP_NUM" | tail -4 | cut -c1-900 >> $O/two_rank.log
   done
   cat $O/two_rank.log ;;
 cmd)
@@ -133,7 +133,7 @@ ab4|ab4b)
     name="${setting%%|*}"; rest="${setting#*|}"; lib="${rest%%|*}"; extra="${rest#*|}"; extra="${extra//,/ }"
     if [ "$lib" != "-" ]; then export FROSTING_LIB="$ROOTD/$lib"; else unset FROSTING_LIB; fi
     for cfg in ${CFG}; do
-      timeout 600 python bench.py --config $cfg --steps ${STEPS:-40} --warmup 10 --no-cpu-baseline --no-extras $extra 2>> $O/$w.err | python -c "
+      timeout 600 python bench.py --config $cfg --steps ${STEPS:-40} --warmup 10 --full --no-cpu-baseline --no-extras $extra 2>> $O/$w.err | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%-10s %-3s %.4f ms/step | ' % ('$name', '$cfg', d['ms_per_step']) + ' '.join('%s %.3f' % (k, v) for k, v in d.get('stage_ms', {}).items()))" >> $O/$w.log

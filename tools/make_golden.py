@@ -40,7 +40,7 @@ def main():
         )
         for k, v in g.items():
             arrs["grad_" + k] = v.cpu().numpy()
-        np.savez_compressed(os.path.join(out_dir, name + ".npz"), **arrs)
+        Hh.save_fixture(os.path.join(out_dir, name + ".npz"), arrs)     # (large arrays: a second file under more/)
         print(name, "R", R, "visible", int(vis.sum()), "bytes", os.path.getsize(os.path.join(out_dir, name + ".npz")))
 
 if __name__ == "__main__":
