@@ -10,6 +10,8 @@ import ctypes as C
 import os
 import subprocess
 
+import torch
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # FROSTING_LIB: another build of the same library (A/B timing of kernel variants in one GPU session; tools/ab.py)
 LIB_PATH = os.environ.get("FROSTING_LIB") or os.path.join(_PKG, "lib", "libfrosting_rasterizer.so")
@@ -118,6 +120,96 @@ class CombineArgs(C.Structure):
                 ("hip_stream", C.c_void_p)]
 
 
+# The parameters of the reference-shaped entry points are fields of the structs: their positional order, written once.
+# (argtypes of the functions and the arguments of a call are both derived from it.)
+FORWARD_POSITIONAL = [name for name, _ in ForwardArgs._fields_[1:ForwardArgs._fields_.index(("hip_stream", C.c_void_p)) + 1]]
+# frg_forward_deferred: the same list, instance_capacity in the place of debug
+FORWARD_DEFERRED_POSITIONAL = ["instance_capacity" if name == "debug" else name for name in FORWARD_POSITIONAL]
+BACKWARD_POSITIONAL = [name for name, _ in BackwardArgs._fields_[1:BackwardArgs._fields_.index(("hip_stream", C.c_void_p)) + 1]]
+
+
+_FIELD_NAMES = {cls: frozenset(name for name, _ in cls._fields_) for cls in (ForwardArgs, BackwardArgs)}
+
+
+def _args(cls, fields):
+    if "modes" in fields:
+        fields.update(mode_fields(fields.pop("modes")))
+    unknown = fields.keys() - _FIELD_NAMES[cls]
+    if unknown:
+        raise TypeError(f"{cls.__name__} has no field {sorted(unknown)}")
+    tensors = []
+    for name, value in fields.items():
+        if isinstance(value, torch.Tensor):
+            tensors.append(value)
+            fields[name] = value.data_ptr() if value.numel() else None
+    a = cls(struct_size=C.sizeof(cls), **fields)
+    a.tensors = tensors        # what the pointers point into lives as long as the struct does
+    return a
+
+
+def forward_args(**fields) -> ForwardArgs:
+    """A filled frg_forward_args.  Pointer fields take a tensor, None or the reference's 'absent' encoding (an empty
+    tensor, DGR/diff_gaussian_rasterization/__init__.py:197-207); modes= takes what mode_fields takes.  The struct keeps
+    every tensor it points into referenced (and, through its callback fields, the scratch chunks)."""
+    return _args(ForwardArgs, fields)
+
+
+def backward_args(**fields) -> BackwardArgs:
+    """A filled frg_backward_args; pointer fields and lifetimes as in forward_args."""
+    return _args(BackwardArgs, fields)
+
+
+def positional(a, order) -> list:
+    """The fields of a filled struct as the arguments of the reference-shaped function with that parameter order."""
+    return [getattr(a, name) for name in order]
+
+
+def ptr(t):
+    """Device pointer of a tensor as a ctypes argument; NULL for None and for the reference's 'absent' encoding (an empty tensor)."""
+    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+
+
+def stream_ptr(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def check(rc: int, what: str) -> int:
+    if rc < 0:
+        raise RuntimeError(f"{what} failed ({rc}): {last_error()}")
+    return rc
+
+
+class Scratch:
+    """A device buffer grown through the C ABI's allocation callbacks (.cb) or by ensure(): reallocated, `slack` times the
+    size asked for, when it is too small.  slack 1.0: the per-call chunks of the reference binding
+    (rasterize_points.cu:27-33,71-78); 1.25: a grow-only arena -- after the first view no allocator call remains on the
+    per-step path (image size and P are constant per model, only R varies -- SURVEY Appendix A-18).
+    The callback holds the tensor's holder, not this object: nothing here forms a cycle, the memory goes with the last reference."""
+
+    def __init__(self, device, slack: float = 1.0):
+        self._held = held = [torch.empty(0, dtype=torch.uint8, device=device)]
+
+        def alloc(_user, nbytes):
+            if held[0].numel() < max(nbytes, 1):
+                held[0] = torch.empty(int(nbytes * slack) + 256, dtype=torch.uint8, device=device)
+            return held[0].data_ptr()
+
+        self._alloc = alloc
+        self.cb = ALLOC_FN(alloc)
+
+    @property
+    def buf(self):
+        return self._held[0]
+
+    @buf.setter
+    def buf(self, tensor):
+        self._held[0] = tensor
+
+    def ensure(self, nbytes):
+        self._alloc(None, nbytes)
+        return self.buf
+
+
 def build(verbose: bool = False) -> str:
     """Compile every HIP translation unit for gfx950 (hipcc cross-compiles on CPU-only hosts)."""
     out = None if verbose else subprocess.DEVNULL
@@ -160,15 +252,9 @@ def lib():
     L.frg_mark_visible.restype = i
     L.frg_mark_visible.argtypes = [i, vp, vp, vp, vp, vp]
     L.frg_forward.restype = i
-    L.frg_forward.argtypes = [ALLOC_FN, ALLOC_FN, ALLOC_FN, vp,
-                              i, i, i, vp, i, i,
-                              vp, vp, vp, vp,
-                              vp, f, vp, vp,
-                              vp, vp, vp,
-                              f, f, i,
-                              vp, vp, i, vp]
+    L.frg_forward.argtypes = [dict(ForwardArgs._fields_)[name] for name in FORWARD_POSITIONAL]
     L.frg_forward_deferred.restype = i
-    L.frg_forward_deferred.argtypes = list(L.frg_forward.argtypes)   # `debug` slot carries instance_capacity
+    L.frg_forward_deferred.argtypes = [dict(ForwardArgs._fields_)[name] for name in FORWARD_DEFERRED_POSITIONAL]
     L.frg_knn_workspace_bytes.restype = sz
     L.frg_knn_workspace_bytes.argtypes = [i]
     L.frg_knn_mean_dist2.restype = i
@@ -196,15 +282,7 @@ def lib():
     L.frg_forward_finish.restype = i
     L.frg_forward_finish.argtypes = [vp, i, C.POINTER(C.c_int)]
     L.frg_backward.restype = i
-    L.frg_backward.argtypes = [i, i, i, i, vp, i, i,
-                               vp, vp, vp,
-                               vp, f, vp, vp,
-                               vp, vp, vp,
-                               f, f, vp,
-                               vp, vp, vp, vp,
-                               vp, vp, vp, vp,
-                               vp, vp, vp, vp, vp,
-                               vp, sz, i, vp]
+    L.frg_backward.argtypes = [dict(BackwardArgs._fields_)[name] for name in BACKWARD_POSITIONAL]
     L.frg_stage_times.restype = i
     L.frg_stage_times.argtypes = [vp, i]
     L.frg_mesh_raster_workspace_bytes.restype = sz

@@ -14,8 +14,7 @@ import torch
 from . import _lib
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
+_ptr = _lib.ptr
 
 
 def _check(P, *tensors):
@@ -35,8 +34,7 @@ def activate(raw_opacity, raw_scale, raw_rot, out=None):
     o, s, r = out if out is not None else (torch.empty_like(raw_opacity), torch.empty_like(raw_scale), torch.empty_like(raw_rot))
     rc = _lib.lib().frg_activate(P, _ptr(raw_opacity), _ptr(raw_scale), _ptr(raw_rot), _ptr(o), _ptr(s), _ptr(r),
                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc < 0:
-        raise RuntimeError(f"frg_activate failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_activate")
     return o, s, r
 
 
@@ -46,8 +44,7 @@ def activate_backward_(opacity, scale, raw_rot, g_opacity, g_scale, g_rot):
     dev = _check(P, opacity, scale, raw_rot, g_opacity, g_scale, g_rot)
     rc = _lib.lib().frg_activate_backward(P, _ptr(opacity), _ptr(scale), _ptr(raw_rot), _ptr(g_opacity), _ptr(g_scale),
                                           _ptr(g_rot), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc < 0:
-        raise RuntimeError(f"frg_activate_backward failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_activate_backward")
     return g_opacity, g_scale, g_rot
 
 
@@ -84,8 +81,7 @@ class _ShellPoints(torch.autograd.Function):
         pts = torch.empty((P, 3), dtype=torch.float32, device=dev)
         rc = _lib.lib().frg_shell_points(P, _ptr(lg), _ptr(cv), _ptr(ci), _ptr(pts),
                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc < 0:
-            raise RuntimeError(f"frg_shell_points failed ({rc}): {_lib.last_error()}")
+        _lib.check(rc, "frg_shell_points")
         ctx.save_for_backward(lg, cv, ci)
         return pts
 
@@ -95,8 +91,7 @@ class _ShellPoints(torch.autograd.Function):
         out = torch.empty_like(lg)
         rc = _lib.lib().frg_shell_points_backward(lg.shape[0], _ptr(lg), _ptr(cv), _ptr(ci), _ptr(g.contiguous()), _ptr(out),
                                                   C.c_void_p(torch.cuda.current_stream(lg.device).cuda_stream))
-        if rc < 0:
-            raise RuntimeError(f"frg_shell_points_backward failed ({rc}): {_lib.last_error()}")
+        _lib.check(rc, "frg_shell_points_backward")
         return out, None, None
 
 

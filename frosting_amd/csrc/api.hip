@@ -6,6 +6,7 @@
 #include "../../include/frosting_rasterizer.h"
 #include "kernels.h"
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -13,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <initializer_list>
 #include <mutex>
 #include <thread>
 
@@ -438,6 +440,18 @@ frg::ViewParams make_view(int P, int D, int M, int width, int height, float tan_
 
 FwdModes default_modes() { return FwdModes{exact_blend(), g_tight_binning.load(), g_async_sh.load(), 0}; }
 
+// frg_forward_args / frg_backward_args grew field by field: a caller built against an earlier header states a smaller
+// struct_size.  One of the accepted generation sizes: *full <- the caller's bytes, the fields it does not know zeroed --
+// every field added after the first generation reads 0 / NULL as "absent / the process default / one call".
+template <class Args>
+bool widen(const Args* a, std::initializer_list<size_t> generations, Args* full)
+{
+    if (!a || std::find(generations.begin(), generations.end(), a->struct_size) == generations.end()) return false;
+    *full = Args{};
+    memcpy(full, a, a->struct_size);
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -593,17 +607,26 @@ int frg_mark_visible(int P, const float* means3D, const float* viewmatrix, const
 // scatter.  capacity > 0: no host synchronisation at all -- the binning buffer is sized for
 // `capacity` instances up front, launches that depend on the counters use device-side values,
 // and the counters travel to a pinned slot that frg_forward_finish() inspects later.
-static int forward_impl(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc, frg_alloc_fn image_alloc, void* user,
-                        int P, int D, int M, const float* background, int width, int height,
-                        const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-                        const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                        const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                        float tan_fovx, float tan_fovy, int prefiltered,
-                        float* out_color, int* radii, int debug, void* hip_stream, int capacity,
-                        const unsigned char* keep_mask = nullptr, const frg::RawInputs* raw = nullptr, const FwdModes* modes = nullptr)
+static int forward_impl(const frg_forward_args& a)
 {
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const FwdModes md = modes ? *modes : default_modes();
+    if (a.instance_capacity < 0) return fail(FRG_EINVAL, "instance_capacity < 0");
+    if (a.forward_only < 0 || a.forward_only > 1) return fail(FRG_EINVAL, "frg_forward_args: forward_only must be 0 or 1");
+    if (a.forward_only && a.instance_capacity > 0)
+        return fail(FRG_EINVAL, "frg_forward_args: forward_only with deferred counters (instance_capacity > 0) is not offered");
+    if (a.exact_blend < 0 || a.exact_blend > 2 || a.tight_binning < 0 || a.tight_binning > 2 || a.async_sh < 0 ||
+        a.async_sh > 4 || a.shell_bary_mode < 0 || a.shell_bary_mode > 1)
+        return fail(FRG_EINVAL, "frg_forward_args: mode out of range (exact_blend %d, tight_binning %d, async_sh %d, shell_bary_mode %d)",
+                    a.exact_blend, a.tight_binning, a.async_sh, a.shell_bary_mode);
+    const int P = a.P, width = a.width, height = a.height, prefiltered = a.prefiltered, capacity = a.instance_capacity;
+    const int debug = capacity > 0 ? 0 : a.debug;     // (deferred counters: no synchronisation, the stage-by-stage one included)
+    const float* const background = a.background;
+    float* const out_color = a.out_color;
+    hipStream_t stream = (hipStream_t)a.hip_stream;
+    FwdModes md = default_modes();
+    md.exact = FwdModes::pick(a.exact_blend, 1, md.exact);
+    md.tight = FwdModes::pick(a.tight_binning, 1, md.tight);
+    md.async_sh = FwdModes::pick(a.async_sh, 3, md.async_sh);
+    md.fwd_only = a.forward_only;
     const int exact = md.exact;
     const int seg_forced = g_bwd_seg_log.load();      // (read once: the size asked of the callback and the carve must agree)
     auto bin_bytes = [seg_forced](int R_, int longest) { return frg::BinningState::carve(nullptr, R_, longest, seg_forced).bytes; };
@@ -613,40 +636,43 @@ static int forward_impl(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc,
         FRG_HIP(hipMemsetAsync(out_color, 0, (size_t)3 * width * height * sizeof(float), stream));
         return 0;
     }
-    const frg::RawInputs rw = raw ? *raw : frg::RawInputs{};
-    if (!viewmatrix || !projmatrix || !cam_pos || !background) return fail(FRG_EINVAL, "null required pointer");
-    if ((means3D == nullptr) == (rw.shell_logits == nullptr))
+    frg::RawInputs rw;
+    rw.raw_opacity = a.raw_opacities; rw.raw_scale = a.raw_scales; rw.raw_rot = a.raw_rotations;
+    rw.shell_logits = a.shell_logits; rw.shell_verts = a.shell_cell_verts; rw.shell_cells = a.shell_cells;
+    rw.bary_mode = a.shell_bary_mode;
+    if (!a.viewmatrix || !a.projmatrix || !a.cam_pos || !background) return fail(FRG_EINVAL, "null required pointer");
+    if ((a.means3D == nullptr) == (rw.shell_logits == nullptr))
         return fail(FRG_EINVAL, "provide exactly one of means3D / shell_logits");
     if (rw.shell_logits && (!rw.shell_verts || !rw.shell_cells))
         return fail(FRG_EINVAL, "shell_logits needs shell_cell_verts and shell_cells");
-    if ((opacities == nullptr) == (rw.raw_opacity == nullptr))
+    if ((a.opacities == nullptr) == (rw.raw_opacity == nullptr))
         return fail(FRG_EINVAL, "provide exactly one of opacities / raw_opacities");
-    if ((shs == nullptr) == (colors_precomp == nullptr))
+    if ((a.shs == nullptr) == (a.colors_precomp == nullptr))
         return fail(FRG_EINVAL, "provide exactly one of shs / colors_precomp");
     if ((rw.raw_scale == nullptr) != (rw.raw_rot == nullptr))
         return fail(FRG_EINVAL, "raw_scales and raw_rotations come together");
-    const bool have_sr = (scales && rotations) || rw.raw_scale;
-    if ((scales || rotations) && rw.raw_scale) return fail(FRG_EINVAL, "provide (scales, rotations) or their raw forms, not both");
-    if (((scales == nullptr) != (rotations == nullptr)) || have_sr == (cov3D_precomp != nullptr))
+    const bool have_sr = (a.scales && a.rotations) || rw.raw_scale;
+    if ((a.scales || a.rotations) && rw.raw_scale) return fail(FRG_EINVAL, "provide (scales, rotations) or their raw forms, not both");
+    if (((a.scales == nullptr) != (a.rotations == nullptr)) || have_sr == (a.cov3D_precomp != nullptr))
         return fail(FRG_EINVAL, "provide exactly one of (scales, rotations) / cov3D_precomp");
-    if (shs && (D < 0 || D > 3 || M < (D + 1) * (D + 1)))
-        return fail(FRG_EINVAL, "SH degree %d needs %d coefficients, got M=%d", D, (D + 1) * (D + 1), M);
-    if (!geometry_alloc || !binning_alloc || !image_alloc) return fail(FRG_EINVAL, "null allocation callback");
+    if (a.shs && (a.D < 0 || a.D > 3 || a.M < (a.D + 1) * (a.D + 1)))
+        return fail(FRG_EINVAL, "SH degree %d needs %d coefficients, got M=%d", a.D, (a.D + 1) * (a.D + 1), a.M);
+    if (!a.geometry_alloc || !a.binning_alloc || !a.image_alloc) return fail(FRG_EINVAL, "null allocation callback");
 
-    frg::ViewParams vp = make_view(P, D, M, width, height, tan_fovx, tan_fovy, scale_modifier, md.tight);
+    frg::ViewParams vp = make_view(P, a.D, a.M, width, height, a.tan_fovx, a.tan_fovy, a.scale_modifier, md.tight);
     // Will this view see only a part of the model?  With an occlusion mask: yes.  Otherwise: what the previous forward of
     // this thread saw (posted by its scatter) -- the SH pass then streams the rows of the visible Gaussians only.
-    vp.sparse_sh = g_sparse_sh.load(std::memory_order_relaxed) && (keep_mask != nullptr || g_mail.sparse_view(P));
+    vp.sparse_sh = g_sparse_sh.load(std::memory_order_relaxed) && (a.keep_mask != nullptr || g_mail.sparse_view(P));
     vp.sh_no_dir = (g_sh_no_dir.load(std::memory_order_relaxed) || md.fwd_only) ? 1 : 0;
     const int T = vp.gx * vp.gy;
 
-    char* geom_chunk = geometry_alloc(user, frg_geometry_bytes(P));
-    char* img_chunk = image_alloc(user, frg_image_bytes(width, height));
+    char* geom_chunk = a.geometry_alloc(a.user, frg_geometry_bytes(P));
+    char* img_chunk = a.image_alloc(a.user, frg_image_bytes(width, height));
     if (!geom_chunk || !img_chunk) return fail(FRG_EALLOC, "allocation callback returned null");
     note_forward(geom_chunk, exact, md.fwd_only != 0);
     const frg::GeomState g = frg::GeomState::carve(geom_chunk, P);
     const frg::ImageState img = frg::ImageState::carve(img_chunk, width, height, g_global_bins.load() != 0);
-    if (!radii) radii = g.internal_radii;   // rasterizer_impl.cu:228-231
+    int* const radii = a.radii ? a.radii : g.internal_radii;   // rasterizer_impl.cu:228-231
 
     PendingCounters* pend = nullptr;
     if (capacity > 0) {
@@ -664,13 +690,13 @@ static int forward_impl(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc,
     if (!img.lds_bins || g_clear_image_state.load(std::memory_order_relaxed)) FRG_HIP(hipMemsetAsync(img_chunk + img.zero_begin, 0, img.zero_bytes, stream));
     else if (prefiltered || capacity > 0) FRG_HIP(hipMemsetAsync(&img.counters->filtered, 0, sizeof(uint32_t), stream));   // (deferred: frg_forward_finish is told `prefiltered` again)
 
-    frg::FwdInputs in{means3D, scales, rotations, opacities, shs, cov3D_precomp, colors_precomp, viewmatrix, projmatrix, cam_pos};
-    in.keep_mask = keep_mask;
+    frg::FwdInputs in{a.means3D, a.scales, a.rotations, a.opacities, a.shs, a.cov3D_precomp, a.colors_precomp, a.viewmatrix, a.projmatrix, a.cam_pos};
+    in.keep_mask = a.keep_mask;
     in.raw = rw;
     // SH colours: nothing before the blend needs them, and the stages in between (scan, scatter, sort) leave the
     // HBM nearly idle -- the colour kernel (the largest single stream of the forward, 192 B per visible Gaussian)
     // runs beside them on a side stream; the blend joins it.
-    const int sh_mode = (shs != nullptr && !rw.shell_logits) ? md.async_sh : 0;   // 0 inside preprocess | side stream forked after: 1 preprocess, 2 scan, 3 scatter
+    const int sh_mode = (a.shs != nullptr && !rw.shell_logits) ? md.async_sh : 0;   // 0 inside preprocess | side stream forked after: 1 preprocess, 2 scan, 3 scatter
     const bool defer_sh = sh_mode != 0 && g_sh_side.ensure();
     bool sh_forked = false;
     // an error return between the fork and the join must not leave the side kernel running on the caller's inputs
@@ -712,7 +738,7 @@ static int forward_impl(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc,
         FRG_HIP(hipStreamWaitEvent(pend->copy_stream, pend->scanned, 0));
         FRG_HIP(hipMemcpyAsync(pend->host, img.counters, sizeof(frg::Counters), hipMemcpyDeviceToHost, pend->copy_stream));
         FRG_HIP(hipEventRecord(pend->ev, pend->copy_stream));
-        char* bin_chunk = binning_alloc(user, bin_bytes(capacity, FRG_SORT_LDS_CAP + 1));
+        char* bin_chunk = a.binning_alloc(a.user, bin_bytes(capacity, FRG_SORT_LDS_CAP + 1));
         if (!bin_chunk) return fail(FRG_EALLOC, "binning allocation callback returned null");
         const frg::BinningState b = frg::BinningState::carve(bin_chunk, capacity, FRG_SORT_LDS_CAP + 1, seg_forced);
         FRG_STAGE(frg::launch_sort_plan(T, nullptr, img.counters->class_count, img.class_tiles, img.ranges, b.big_plan, (uint32_t)capacity, stream), "sort plan");
@@ -741,7 +767,7 @@ static int forward_impl(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc,
             if (r > 0x7fffffffu) return fail(FRG_EINVAL, "num_rendered overflows int32");
             if (r > 0) {
                 R = (int)r;
-                char* bin_chunk = binning_alloc(user, bin_bytes(R, FRG_SORT_LDS_CAP + 1));
+                char* bin_chunk = a.binning_alloc(a.user, bin_bytes(R, FRG_SORT_LDS_CAP + 1));
                 if (!bin_chunk) return fail(FRG_EALLOC, "binning allocation callback returned null");
                 b = frg::BinningState::carve(bin_chunk, R, FRG_SORT_LDS_CAP + 1, seg_forced);
                 if (g_mail.long_lists)
@@ -771,7 +797,7 @@ static int forward_impl(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc,
     note_rendered(geom_chunk, R);
 
     if (!early) {
-        char* bin_chunk = binning_alloc(user, bin_bytes(R, max_tile));
+        char* bin_chunk = a.binning_alloc(a.user, bin_bytes(R, max_tile));
         if (!bin_chunk) return fail(FRG_EALLOC, "binning allocation callback returned null");
         b = frg::BinningState::carve(bin_chunk, R, max_tile, seg_forced);
     }
@@ -833,9 +859,11 @@ int frg_forward(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc, frg_all
                 float tan_fovx, float tan_fovy, int prefiltered,
                 float* out_color, int* radii, int debug, void* hip_stream)
 {
-    return forward_impl(geometry_alloc, binning_alloc, image_alloc, user, P, D, M, background, width, height, means3D, shs,
-                        colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                        cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, radii, debug, hip_stream, 0);
+    // (the parameters are the struct's fields up to hip_stream, in its order; the later fields stay 0 / NULL: absent)
+    return forward_impl(frg_forward_args{sizeof(frg_forward_args), geometry_alloc, binning_alloc, image_alloc, user, P, D, M, background,
+                                         width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                                         cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
+                                         radii, debug, hip_stream});
 }
 
 int frg_forward_deferred(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc, frg_alloc_fn image_alloc, void* user,
@@ -847,9 +875,10 @@ int frg_forward_deferred(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc
                          float* out_color, int* radii, int instance_capacity, void* hip_stream)
 {
     if (instance_capacity <= 0) return fail(FRG_EINVAL, "instance_capacity must be positive");
-    return forward_impl(geometry_alloc, binning_alloc, image_alloc, user, P, D, M, background, width, height, means3D, shs,
-                        colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                        cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, radii, 0, hip_stream, instance_capacity);
+    return forward_impl(frg_forward_args{sizeof(frg_forward_args), geometry_alloc, binning_alloc, image_alloc, user, P, D, M, background,
+                                         width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                                         cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
+                                         radii, /* debug */ 0, hip_stream, instance_capacity});
 }
 
 int frg_forward_ex(const frg_forward_args* a)
@@ -858,37 +887,11 @@ int frg_forward_ex(const frg_forward_args* a)
     // per-call modes, with forward_only
     const size_t v1 = offsetof(frg_forward_args, raw_opacities), v2 = offsetof(frg_forward_args, exact_blend),
                  v3 = offsetof(frg_forward_args, forward_only);
-    if (!a || (a->struct_size != sizeof(frg_forward_args) && a->struct_size != v1 && a->struct_size != v2 && a->struct_size != v3))
+    frg_forward_args full;
+    if (!widen(a, {sizeof(frg_forward_args), v3, v2, v1}, &full))
         return fail(FRG_EINVAL, "frg_forward_args: struct_size %zu, this library expects %zu (or %zu, %zu, %zu)", a ? a->struct_size : (size_t)0,
                     sizeof(frg_forward_args), v3, v2, v1);
-    if (a->instance_capacity < 0) return fail(FRG_EINVAL, "instance_capacity < 0");
-    frg::RawInputs rw;
-    if (a->struct_size >= v2) {
-        rw.raw_opacity = a->raw_opacities; rw.raw_scale = a->raw_scales; rw.raw_rot = a->raw_rotations;
-        rw.shell_logits = a->shell_logits; rw.shell_verts = a->shell_cell_verts; rw.shell_cells = a->shell_cells;
-    }
-    FwdModes md = default_modes();
-    if (a->struct_size == sizeof(frg_forward_args)) {
-        if (a->forward_only < 0 || a->forward_only > 1) return fail(FRG_EINVAL, "frg_forward_args: forward_only must be 0 or 1");
-        if (a->forward_only && a->instance_capacity > 0)
-            return fail(FRG_EINVAL, "frg_forward_args: forward_only with deferred counters (instance_capacity > 0) is not offered");
-        md.fwd_only = a->forward_only;
-    }
-    if (a->struct_size >= v3) {
-        if (a->exact_blend < 0 || a->exact_blend > 2 || a->tight_binning < 0 || a->tight_binning > 2 || a->async_sh < 0 ||
-            a->async_sh > 4 || a->shell_bary_mode < 0 || a->shell_bary_mode > 1)
-            return fail(FRG_EINVAL, "frg_forward_args: mode out of range (exact_blend %d, tight_binning %d, async_sh %d, shell_bary_mode %d)",
-                        a->exact_blend, a->tight_binning, a->async_sh, a->shell_bary_mode);
-        md.exact = FwdModes::pick(a->exact_blend, 1, md.exact);
-        md.tight = FwdModes::pick(a->tight_binning, 1, md.tight);
-        md.async_sh = FwdModes::pick(a->async_sh, 3, md.async_sh);
-        rw.bary_mode = a->shell_bary_mode;
-    }
-    return forward_impl(a->geometry_alloc, a->binning_alloc, a->image_alloc, a->user, a->P, a->D, a->M, a->background,
-                        a->width, a->height, a->means3D, a->shs, a->colors_precomp, a->opacities, a->scales,
-                        a->scale_modifier, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->cam_pos,
-                        a->tan_fovx, a->tan_fovy, a->prefiltered, a->out_color, a->radii,
-                        a->instance_capacity > 0 ? 0 : a->debug, a->hip_stream, a->instance_capacity, a->keep_mask, &rw, &md);
+    return forward_impl(full);
 }
 
 int frg_forward_finish(const char* image_buffer, int prefiltered, int* num_rendered)
@@ -912,35 +915,34 @@ int frg_forward_finish(const char* image_buffer, int prefiltered, int* num_rende
 
 }  // extern "C"
 
-static int backward_impl(int P, int D, int M, int R, const float* background, int width, int height,
-                 const float* means3D, const float* shs, const float* colors_precomp,
-                 const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                 const float* viewmatrix, const float* projmatrix, const float* campos,
-                 float tan_fovx, float tan_fovy, const int* radii,
-                 char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
-                 float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                 float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                 char* workspace, size_t workspace_bytes, int debug, void* hip_stream,
-                 const frg::RawInputs& rw, float* dL_dshell_logits, float* dL_dshell_verts, int exact_mode = 0, int phase = 0,
-                 unsigned char* row_live = nullptr, int range_first = 0, int range_count = 0)
+static int backward_impl(const frg_backward_args& a)
 {
-    hipStream_t stream = (hipStream_t)hip_stream;
+    if (a.exact_blend < 0 || a.exact_blend > 2 || a.shell_bary_mode < 0 || a.shell_bary_mode > 1)
+        return fail(FRG_EINVAL, "frg_backward_args: mode out of range (exact_blend %d, shell_bary_mode %d)", a.exact_blend, a.shell_bary_mode);
+    const int P = a.P, R = a.R, width = a.width, height = a.height, debug = a.debug, phase = a.phase;
+    const float *const means3D = a.means3D, *const shs = a.shs, *const scales = a.scales, *const background = a.background, *const dL_dpix = a.dL_dpix;
+    char *const geom_buffer = a.geom_buffer, *const image_buffer = a.image_buffer, *const workspace = a.workspace;
+    hipStream_t stream = (hipStream_t)a.hip_stream;
+    frg::RawInputs rw;
+    rw.raw_opacity = a.raw_opacities; rw.raw_scale = a.raw_scales; rw.raw_rot = a.raw_rotations;
+    rw.shell_logits = a.shell_logits; rw.shell_verts = a.shell_cell_verts; rw.shell_cells = a.shell_cells;
+    rw.bary_mode = a.shell_bary_mode;
     if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(FRG_EINVAL, "bad sizes");
     if (P == 0) return FRG_OK;
-    if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dpix || !background || !viewmatrix || !projmatrix || !campos)
+    if (!geom_buffer || !a.binning_buffer || !image_buffer || !dL_dpix || !background || !a.viewmatrix || !a.projmatrix || !a.campos)
         return fail(FRG_EINVAL, "null required pointer");
     if ((means3D == nullptr) == (rw.shell_logits == nullptr)) return fail(FRG_EINVAL, "provide exactly one of means3D / shell_logits");
-    if (rw.shell_logits && (!rw.shell_verts || !rw.shell_cells || !dL_dshell_logits))
+    if (rw.shell_logits && (!rw.shell_verts || !rw.shell_cells || !a.dL_dshell_logits))
         return fail(FRG_EINVAL, "shell_logits needs shell_cell_verts, shell_cells and dL_dshell_logits");
-    if (!dL_dmean2D || !dL_dopacity || !dL_dmean3D) return fail(FRG_EINVAL, "null gradient output");
+    if (!a.dL_dmean2D || !a.dL_dopacity || !a.dL_dmean3D) return fail(FRG_EINVAL, "null gradient output");
     // intermediates of the chain may be left out when the caller has no use for them: dL_dcolor when the SH rows are
     // written (it is then only the factor of dL_dsh), dL_dcov3D when the covariance comes from scales / rotations
-    if (!dL_dcolor && !(shs && dL_dsh)) return fail(FRG_EINVAL, "dL_dcolor may only be NULL when shs and dL_dsh are given");
-    if (!dL_dcov3D && cov3D_precomp) return fail(FRG_EINVAL, "dL_dcov3D may only be NULL without cov3D_precomp");
+    if (!a.dL_dcolor && !(shs && a.dL_dsh)) return fail(FRG_EINVAL, "dL_dcolor may only be NULL when shs and dL_dsh are given");
+    if (!a.dL_dcov3D && a.cov3D_precomp) return fail(FRG_EINVAL, "dL_dcov3D may only be NULL without cov3D_precomp");
     if ((rw.raw_scale == nullptr) != (rw.raw_rot == nullptr)) return fail(FRG_EINVAL, "raw_scales and raw_rotations come together");
-    if (((scales && (!dL_dscale || !dL_drot || !rotations))) || (rw.raw_scale && (!dL_dscale || !dL_drot)))
+    if (((scales && (!a.dL_dscale || !a.dL_drot || !a.rotations))) || (rw.raw_scale && (!a.dL_dscale || !a.dL_drot)))
         return fail(FRG_EINVAL, "null gradient output for a provided input");
-    if (workspace_bytes < frg_backward_workspace_bytes(P, R) || !workspace)
+    if (a.workspace_bytes < frg_backward_workspace_bytes(P, R) || !workspace)
         return fail(FRG_EALLOC, "workspace too small: need %zu bytes", frg_backward_workspace_bytes(P, R));
     // R sizes the slots and the backward blend's item list: fewer than the forward rendered would overrun them.  (More is
     // fine -- a deferred forward's capacity: where the forward's checkpoints lie in the binning chunk is taken from what the
@@ -954,10 +956,10 @@ static int backward_impl(int P, int D, int M, int R, const float* background, in
     //     ctx), else BOTH instantiations are launched and each leaves at once unless the stamp names it (exact = -1 below);
     //   * forward_only: a note that says "an ordinary forward" lets the call through (a forward_only stamp then still leaves
     //     the kernels without work); anything else -- no note, or a note that says forward_only -- is settled by reading the
-    //     stamp back, one blocking 4-byte copy, which also tells the arithmetic.
+    //     stamp back, one blocking copy of the forward's counters, which also tells the arithmetic.
     //   * R: a note that says the forward rendered MORE instances than this call's R (slots and item lists would overrun) is
     //     checked against the stamped count the same way before the call is refused.
-    int exact = exact_mode == 0 ? -1 : FwdModes::pick(exact_mode, 1, 0);
+    int exact = a.exact_blend == 0 ? -1 : FwdModes::pick(a.exact_blend, 1, 0);
     const int noted_rendered = forward_rendered(geom_buffer);
     if ((forward_was_forward_only(geom_buffer) != 0 || (noted_rendered >= 0 && R < noted_rendered)) && phase != 2) {
         frg::Counters* host = pinned_counters();
@@ -974,29 +976,28 @@ static int backward_impl(int P, int D, int M, int R, const float* background, in
             return fail(FRG_EINVAL, "R = %d, but the forward that filled this geometry buffer rendered %u instances", R, host->num_rendered);
         if (exact < 0) exact = (flags & FRG_FWD_EXACT) ? 1 : 0;
     }
-    (void)colors_precomp;  // forward copied precomputed colours into the geometry state
 
     // Nothing here depends on the process-wide binning options: every field of the three chunks that the
     // backward reads is carved from (P, W, H, R) alone (the option-dependent matrices of the binning stage
     // come last in the image chunk), and the kernels take the forward's binning mode from the counters it
     // stamped.  "exact_blend" only selects the arithmetic of this backward's own blend pass.
-    frg::ViewParams vp = make_view(P, D, M, width, height, tan_fovx, tan_fovy, scale_modifier, 0);
+    frg::ViewParams vp = make_view(P, a.D, a.M, width, height, a.tan_fovx, a.tan_fovy, a.scale_modifier, 0);
     const frg::GeomState g = frg::GeomState::carve(geom_buffer, P);
     const frg::ImageState img = frg::ImageState::carve(image_buffer, width, height, false);
-    const frg::BinningState b = frg::BinningState::carve(binning_buffer, R, 0);
+    const frg::BinningState b = frg::BinningState::carve(a.binning_buffer, R, 0);
     float* slots = reinterpret_cast<float*>(workspace);
     float* sums = reinterpret_cast<float*>(workspace + slots_bytes(R));
     unsigned long long* live_masks = phase == 1 ? reinterpret_cast<unsigned long long*>(workspace + slots_bytes(R) + sums_bytes(P)) : nullptr;
     float* dir_terms = reinterpret_cast<float*>(workspace + slots_bytes(R) + sums_bytes(P) + live_mask_bytes(P) + pack_scratch_bytes(P));
     if (phase < 0 || phase > 2) return fail(FRG_EINVAL, "frg_backward_args: phase %d (0 whole | 1 blend + slot sums | 2 the rest)", phase);
-    if (!radii) radii = g.internal_radii;   // rasterizer_impl.cu:375-377
+    const int* const radii = a.radii ? a.radii : g.internal_radii;   // rasterizer_impl.cu:375-377
 
-    frg::FwdInputs in{means3D, scales, rotations, nullptr, shs, cov3D_precomp, colors_precomp, viewmatrix, projmatrix, campos};
+    frg::FwdInputs in{means3D, scales, a.rotations, nullptr, shs, a.cov3D_precomp, a.colors_precomp, a.viewmatrix, a.projmatrix, a.campos};
     in.raw = rw;
-    frg::BwdOutputs out{dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot};
-    out.dL_dshell_logits = dL_dshell_logits;
-    out.dL_dshell_verts = dL_dshell_verts;
-    out.row_live = row_live;
+    frg::BwdOutputs out{a.dL_dmean2D, a.dL_dconic, a.dL_dopacity, a.dL_dcolor, a.dL_dmean3D, a.dL_dcov3D, a.dL_dsh, a.dL_dscale, a.dL_drot};
+    out.dL_dshell_logits = a.dL_dshell_logits;
+    out.dL_dshell_verts = a.dL_dshell_cell_verts;
+    out.row_live = a.row_live;
     const int pbw_flags = phase == 1 ? FRG_PBW_SUMS_ONLY : phase == 2 ? FRG_PBW_FROM_SUMS : 0;
     if (phase == 2) {     // the sums are in the workspace: one launch, no slot reduction, hence no 16-wave form either
         if (!phase1_matches(workspace, geom_buffer, image_buffer, P, R))
@@ -1006,11 +1007,11 @@ static int backward_impl(int P, int D, int M, int R, const float* background, in
         return FRG_OK;
     }
     if (phase == 1) note_phase1(workspace, geom_buffer, image_buffer, P, R);
-    const bool ranged = range_count > 0;
+    const bool ranged = a.range_count > 0;
     if (ranged) {
         if (phase != 1) return fail(FRG_EINVAL, "frg_backward_args: a range is offered with phase 1 only (phase %d)", phase);
-        if (range_first < 0 || range_first % 256 != 0 || (long long)range_first + range_count > P)
-            return fail(FRG_EINVAL, "frg_backward_args: range [%d, +%d) of %d Gaussians (range_first: a multiple of 256)", range_first, range_count, P);
+        if (a.range_first < 0 || a.range_first % 256 != 0 || (long long)a.range_first + a.range_count > P)
+            return fail(FRG_EINVAL, "frg_backward_args: range [%d, +%d) of %d Gaussians (range_first: a multiple of 256)", a.range_first, a.range_count, P);
     }
     const bool probe_bwd = (g_probe.load() & 2) && g_probe_side.ensure();
     if (probe_bwd) {   // timing experiment: the per-Gaussian backward beside the blend (it reads the previous frame's slots)
@@ -1020,7 +1021,7 @@ static int backward_impl(int P, int D, int M, int R, const float* background, in
         FRG_HIP(frg::launch_preprocess_bwd(P, vp, in, radii, g, img, slots, out, g_ablate.load(), pbw_flags, true, g_probe_side.stream, sums));
         FRG_HIP(hipEventRecord(g_probe_side.join, g_probe_side.stream));
     }
-    if (!ranged || range_first == 0) {
+    if (!ranged || a.range_first == 0) {
         StageScope sc_(ST_BLEND_BWD, stream);
         if (exact != 0)
             FRG_STAGE(frg::launch_blend_bwd_exact(vp, g, img, b, background, dL_dpix, slots, (uint32_t)R, g_bwd_batch.load(), stream, exact < 0), "blend_bwd");
@@ -1031,7 +1032,7 @@ static int backward_impl(int P, int D, int M, int R, const float* background, in
     if (ranged) {      // phase 1 in pieces: the plain kernel over this range, whatever its waves own (no 16-wave side launch)
         StageScope sc_(ST_PREPROCESS_BWD, stream);
         FRG_STAGE(frg::launch_preprocess_bwd(P, vp, in, radii, g, img, slots, out, g_ablate.load(), pbw_flags | FRG_PBW_NO_HEAVY_LAUNCH, false, stream, sums,
-                                             live_masks, dir_terms, range_first, range_count), "preprocess_bwd (phase 1, range)");
+                                             live_masks, dir_terms, a.range_first, a.range_count), "preprocess_bwd (phase 1, range)");
         return FRG_OK;
     }
     {
@@ -1070,10 +1071,12 @@ int frg_backward(int P, int D, int M, int R, const float* background, int width,
                  float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                  char* workspace, size_t workspace_bytes, int debug, void* hip_stream)
 {
-    return backward_impl(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
-                         cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
-                         image_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                         dL_dscale, dL_drot, workspace, workspace_bytes, debug, hip_stream, frg::RawInputs{}, nullptr, nullptr);
+    // (the parameters are the struct's fields up to hip_stream, in its order; the later fields stay 0 / NULL: absent)
+    return backward_impl(frg_backward_args{sizeof(frg_backward_args), P, D, M, R, background, width, height, means3D, shs, colors_precomp,
+                                           scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
+                                           tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D, dL_dconic,
+                                           dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, workspace,
+                                           workspace_bytes, debug, hip_stream});
 }
 
 int frg_backward_ex(const frg_backward_args* a)
@@ -1081,29 +1084,11 @@ int frg_backward_ex(const frg_backward_args* a)
     // five generations of the struct: up to shell_*, + exact_blend / shell_bary_mode, + phase, + row_live, + range_first / range_count
     const size_t b1 = offsetof(frg_backward_args, exact_blend), b2 = offsetof(frg_backward_args, phase), b3 = offsetof(frg_backward_args, row_live),
                  b4 = offsetof(frg_backward_args, range_first);
-    if (!a || (a->struct_size != sizeof(frg_backward_args) && a->struct_size != b1 && a->struct_size != b2 && a->struct_size != b3 && a->struct_size != b4))
+    frg_backward_args full;
+    if (!widen(a, {sizeof(frg_backward_args), b4, b3, b2, b1}, &full))
         return fail(FRG_EINVAL, "frg_backward_args: struct_size %zu, this library expects %zu (or %zu, %zu, %zu, %zu)", a ? a->struct_size : (size_t)0,
                     sizeof(frg_backward_args), b4, b3, b2, b1);
-    frg::RawInputs rw;
-    rw.raw_opacity = a->raw_opacities; rw.raw_scale = a->raw_scales; rw.raw_rot = a->raw_rotations;
-    rw.shell_logits = a->shell_logits; rw.shell_verts = a->shell_cell_verts; rw.shell_cells = a->shell_cells;
-    int exact_mode = 0;
-    const int phase = a->struct_size >= b3 ? a->phase : 0;
-    unsigned char* row_live = a->struct_size >= b4 ? a->row_live : nullptr;
-    const bool has_range = a->struct_size == sizeof(frg_backward_args);
-    if (a->struct_size >= b2) {
-        if (a->exact_blend < 0 || a->exact_blend > 2 || a->shell_bary_mode < 0 || a->shell_bary_mode > 1)
-            return fail(FRG_EINVAL, "frg_backward_args: mode out of range (exact_blend %d, shell_bary_mode %d)", a->exact_blend, a->shell_bary_mode);
-        exact_mode = a->exact_blend;
-        rw.bary_mode = a->shell_bary_mode;
-    }
-    return backward_impl(a->P, a->D, a->M, a->R, a->background, a->width, a->height, a->means3D, a->shs, a->colors_precomp,
-                         a->scales, a->scale_modifier, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
-                         a->tan_fovx, a->tan_fovy, a->radii, a->geom_buffer, a->binning_buffer, a->image_buffer, a->dL_dpix,
-                         a->dL_dmean2D, a->dL_dconic, a->dL_dopacity, a->dL_dcolor, a->dL_dmean3D, a->dL_dcov3D, a->dL_dsh,
-                         a->dL_dscale, a->dL_drot, a->workspace, a->workspace_bytes, a->debug, a->hip_stream, rw,
-                         a->dL_dshell_logits, a->dL_dshell_cell_verts, exact_mode, phase, row_live, has_range ? a->range_first : 0,
-                         has_range ? a->range_count : 0);
+    return backward_impl(full);
 }
 
 int frg_sh_color_grad(int P, const char* geom_buffer, const int* radii, const float* dL_dcolors,

@@ -16,11 +16,6 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .parallel import _Arena
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 def _f32(t):
@@ -56,33 +51,29 @@ class _RasterizeRaw(torch.autograd.Function):
         inputs = (shs, raw_opacity, raw_scale, raw_rot, means3D, shell_logits, shell_cell_verts, shell_cells, keep_mask, means2D)
         t = _RasterizeRaw._views(inputs)
         cam = dict(bg=_f32(s.bg), view=_f32(s.viewmatrix), proj=_f32(s.projmatrix), campos=_f32(s.campos))
-        modes = _lib.mode_fields(opts.get("modes"))
+        modes = dict(opts.get("modes") or {})
         if not any(ctx.needs_input_grad):      # no parameter needs a gradient (or torch.no_grad()): nothing is kept for a backward
             modes["forward_only"] = 1
         bary_mode = 0 if opts.get("use_softmax_for_bary_coords", True) else 1
         with torch.cuda.device(dev):
             color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
             radii = torch.empty((P,), dtype=torch.int32, device=dev)
-            geom, binning, img = _Arena(dev, 1.0), _Arena(dev, 1.0), _Arena(dev, 1.0)
-            a = _lib.ForwardArgs(
-                struct_size=C.sizeof(_lib.ForwardArgs), geometry_alloc=geom.cb, binning_alloc=binning.cb, image_alloc=img.cb,
-                user=None, P=P, D=int(s.sh_degree), M=int(t["shs"].shape[1]), background=_p(cam["bg"]), width=W, height=H,
-                means3D=_p(t["means"]), shs=_p(t["shs"]), colors_precomp=None, opacities=None, scales=None,
-                scale_modifier=float(s.scale_modifier), rotations=None, cov3D_precomp=None, viewmatrix=_p(cam["view"]),
-                projmatrix=_p(cam["proj"]), cam_pos=_p(cam["campos"]), tan_fovx=float(s.tanfovx), tan_fovy=float(s.tanfovy),
-                prefiltered=int(bool(s.prefiltered)), out_color=color.data_ptr(), radii=radii.data_ptr(), debug=int(bool(s.debug)),
-                hip_stream=torch.cuda.current_stream(dev).cuda_stream, instance_capacity=0, keep_mask=_p(t["mask"]),
-                raw_opacities=_p(t["ro"]), raw_scales=_p(t["rs"]), raw_rotations=_p(t["rr"]), shell_logits=_p(t["lg"]),
-                shell_cell_verts=_p(t["cv"]), shell_cells=_p(t["ci"]), shell_bary_mode=bary_mode, **modes)
-            R = L.frg_forward_ex(C.byref(a))
-        if R < 0:
-            raise RuntimeError(f"frg_forward_ex failed ({R}): {_lib.last_error()}")
+            geom, binning, img = (_lib.Scratch(dev) for _ in range(3))
+            a = _lib.forward_args(
+                geometry_alloc=geom.cb, binning_alloc=binning.cb, image_alloc=img.cb, P=P, D=int(s.sh_degree),
+                M=int(t["shs"].shape[1]), background=cam["bg"], width=W, height=H, means3D=t["means"], shs=t["shs"],
+                scale_modifier=float(s.scale_modifier), viewmatrix=cam["view"], projmatrix=cam["proj"], cam_pos=cam["campos"],
+                tan_fovx=float(s.tanfovx), tan_fovy=float(s.tanfovy), prefiltered=int(bool(s.prefiltered)), out_color=color,
+                radii=radii, debug=int(bool(s.debug)), hip_stream=torch.cuda.current_stream(dev).cuda_stream, keep_mask=t["mask"],
+                raw_opacities=t["ro"], raw_scales=t["rs"], raw_rotations=t["rr"], shell_logits=t["lg"], shell_cell_verts=t["cv"],
+                shell_cells=t["ci"], shell_bary_mode=bary_mode, modes=modes)
+            R = _lib.check(L.frg_forward_ex(C.byref(a)), "frg_forward_ex")
         # the INPUT tensors are saved (autograd's version counters then catch an in-place optimizer step between this
         # forward and its backward); their float32 views are re-derived in backward -- free for contiguous float32
         ctx.save_for_backward(*[x for x in inputs if x is not None])
         ctx.present = [x is not None for x in inputs]
         ctx.cam, ctx.settings, ctx.R, ctx.bufs, ctx.radii = cam, s, R, (geom, binning, img), radii
-        ctx.bary_mode, ctx.exact = bary_mode, modes["exact_blend"]
+        ctx.bary_mode, ctx.exact = bary_mode, a.exact_blend
         ctx.cv_shape = None if shell_cell_verts is None else tuple(shell_cell_verts.shape)
         ctx.ro_shape = tuple(raw_opacity.shape)
         ctx.mark_non_differentiable(radii)
@@ -112,22 +103,17 @@ class _RasterizeRaw(torch.autograd.Function):
                 ws = int(L.frg_backward_workspace_bytes(P, R))
                 work = torch.empty(ws, dtype=torch.uint8, device=dev)
                 gp = g_color.detach().to(torch.float32).contiguous()
-                a = _lib.BackwardArgs(
-                    struct_size=C.sizeof(_lib.BackwardArgs), P=P, D=int(s.sh_degree), M=M, R=R, background=_p(cam["bg"]), width=W,
-                    height=H, means3D=_p(t["means"]), shs=_p(t["shs"]), colors_precomp=None, scales=None,
-                    scale_modifier=float(s.scale_modifier), rotations=None, cov3D_precomp=None, viewmatrix=_p(cam["view"]),
-                    projmatrix=_p(cam["proj"]), campos=_p(cam["campos"]), tan_fovx=float(s.tanfovx), tan_fovy=float(s.tanfovy),
-                    radii=ctx.radii.data_ptr(), geom_buffer=geom.buf.data_ptr(), binning_buffer=binning.buf.data_ptr(),
-                    image_buffer=img.buf.data_ptr(), dL_dpix=gp.data_ptr(), dL_dmean2D=_p(g["m2"]), dL_dconic=None,
-                    dL_dopacity=_p(g["op"]), dL_dcolor=_p(g["col"]), dL_dmean3D=_p(g["m3"]), dL_dcov3D=_p(g["cov"]),
-                    dL_dsh=_p(g["sh"]), dL_dscale=_p(g["sc"]), dL_drot=_p(g["rot"]), workspace=work.data_ptr(), workspace_bytes=ws,
-                    debug=int(bool(s.debug)), hip_stream=torch.cuda.current_stream(dev).cuda_stream,
-                    raw_opacities=_p(t["ro"]), raw_scales=_p(t["rs"]), raw_rotations=_p(t["rr"]), shell_logits=_p(t["lg"]),
-                    shell_cell_verts=_p(t["cv"]), shell_cells=_p(t["ci"]), dL_dshell_logits=_p(g["lg"]),
-                    dL_dshell_cell_verts=_p(g["cv"]), exact_blend=ctx.exact, shell_bary_mode=ctx.bary_mode)
-                rc = L.frg_backward_ex(C.byref(a))
-                if rc < 0:
-                    raise RuntimeError(f"frg_backward_ex failed ({rc}): {_lib.last_error()}")
+                a = _lib.backward_args(
+                    P=P, D=int(s.sh_degree), M=M, R=R, background=cam["bg"], width=W, height=H, means3D=t["means"], shs=t["shs"],
+                    scale_modifier=float(s.scale_modifier), viewmatrix=cam["view"], projmatrix=cam["proj"], campos=cam["campos"],
+                    tan_fovx=float(s.tanfovx), tan_fovy=float(s.tanfovy), radii=ctx.radii, geom_buffer=geom.buf,
+                    binning_buffer=binning.buf, image_buffer=img.buf, dL_dpix=gp, dL_dmean2D=g["m2"], dL_dopacity=g["op"],
+                    dL_dcolor=g["col"], dL_dmean3D=g["m3"], dL_dcov3D=g["cov"], dL_dsh=g["sh"], dL_dscale=g["sc"], dL_drot=g["rot"],
+                    workspace=work, workspace_bytes=ws, debug=int(bool(s.debug)), hip_stream=torch.cuda.current_stream(dev).cuda_stream,
+                    raw_opacities=t["ro"], raw_scales=t["rs"], raw_rotations=t["rr"], shell_logits=t["lg"], shell_cell_verts=t["cv"],
+                    shell_cells=t["ci"], dL_dshell_logits=g["lg"], dL_dshell_cell_verts=g["cv"], exact_blend=ctx.exact,
+                    shell_bary_mode=ctx.bary_mode)
+                _lib.check(L.frg_backward_ex(C.byref(a)), "frg_backward_ex")
                 work.record_stream(torch.cuda.current_stream(dev))
         g_cv = None if out["cv"] is None else out["cv"].reshape(ctx.cv_shape)
         # settings, opts, shs, raw_opacity, raw_scale, raw_rot, means3D, shell_logits, shell_cell_verts, shell_cells, keep_mask,

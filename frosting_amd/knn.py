@@ -35,8 +35,7 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
         rc = L.frg_knn_mean_dist2(P, C.c_void_p(pts.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(base),
                                   ws.numel() - (base - ws.data_ptr()), C.c_void_p(stream.cuda_stream))
         ws.record_stream(stream)
-    if rc < 0:
-        raise RuntimeError(f"frg_knn_mean_dist2 failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_knn_mean_dist2")
     return out
 
 

@@ -62,8 +62,7 @@ def photometric_loss_and_grad(image: torch.Tensor, target: torch.Tensor, lambda_
                                     C.c_void_p(ws.data_ptr()), ws.numel(),
                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         ws.record_stream(torch.cuda.current_stream(dev))
-    if rc < 0:
-        raise RuntimeError(f"frg_photometric_loss failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_photometric_loss")
     return loss, (grad.view(shape) if need_grad else None)
 
 

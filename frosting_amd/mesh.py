@@ -56,8 +56,7 @@ def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
         rc = L.frg_mesh_rasterize(V, F, C.c_void_p(p.data_ptr()) if V else None, C.c_void_p(t.data_ptr()) if F else None,
                                   W, H, C.c_void_p(rast.data_ptr()), C.c_void_p(work.data_ptr()), work.numel(),
                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc < 0:
-        raise RuntimeError(f"frg_mesh_rasterize failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_mesh_rasterize")
     return rast, None
 
 
@@ -116,8 +115,7 @@ def visible_face_mask(verts, faces, full_proj_transform, height, width, glctx=No
         rc = L.frg_mesh_visible_faces(V, F, C.c_void_p(pos.data_ptr()) if V else None, C.c_void_p(t.data_ptr()) if F else None, W, H,
                                       C.c_void_p(mask.data_ptr()) if F else None, C.c_void_p(work.data_ptr()), work.numel(),
                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc < 0:
-        raise RuntimeError(f"frg_mesh_visible_faces failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_mesh_visible_faces")
     return mask
 
 
@@ -145,8 +143,7 @@ def occlusion_keep_mask(verts, faces, full_proj_transform, height, width, point_
         rc = L.frg_mesh_occlusion_mask(V, F, ptr(v), ptr(m), ptr(t), W, H, n_shell, ptr(cells), int(n_background), ptr(keep),
                                        ptr(face_mask), C.c_void_p(work.data_ptr()), work.numel(),
                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc < 0:
-        raise RuntimeError(f"frg_mesh_occlusion_mask failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_mesh_occlusion_mask")
     return (keep, face_mask) if return_face_mask else keep
 
 

@@ -148,8 +148,7 @@ class FlatAdam:
                                           self._ends, lrs, self._period, self._head, head_lrs, len(self.names),
                                           self.betas[0], self.betas[1], self.eps,
                                           self.steps + 1, float(grad_scale), stream)
-        if rc < 0:
-            raise RuntimeError(f"frg_adam_step failed ({rc}): {_lib.last_error()}")
+        _lib.check(rc, "frg_adam_step")
         self.steps += 1                       # only a step that ran advances the bias correction
         return self.params
 
@@ -231,8 +230,7 @@ class ShardedFlatAdam(FlatAdam):
                                                 C.c_void_p(self.exp_avg.data_ptr()), C.c_void_p(self.exp_avg_sq.data_ptr()),
                                                 self._ends, (C.c_float * n)(*lrs), self._period, self._head, (C.c_float * n)(*head_lrs), n,
                                                 self.betas[0], self.betas[1], self.eps, self.steps + 1, float(grad_scale), stream)
-            if rc < 0:
-                raise RuntimeError(f"frg_adam_step_shard failed ({rc}): {_lib.last_error()}")
+            _lib.check(rc, "frg_adam_step_shard")
         # 3. every rank's updated shard to every rank
         dist.all_gather_into_tensor(self.flat_padded, mine.clone(), group=self.group)
         self.steps += 1

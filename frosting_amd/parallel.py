@@ -19,6 +19,8 @@ import torch
 
 from . import _lib
 
+_Arena, _p = _lib.Scratch, _lib.ptr     # (the names tests/test_gpu_parity.py imports from here)
+
 PARAM_ORDER = ("means3D", "scales", "rotations", "opacities", "shs")
 SEGMENT_ALIGN = 4   # floats: every parameter's segment of the flat layout starts on a 16-byte boundary
 
@@ -50,8 +52,7 @@ def _hip_sh_reducer(ex: "GradientExchange"):
     rc = L.frg_sh_grad_from_views(P, ex.sh_degree, K, ex.gathered.shape[0], _p(ex.means3D),
                                   C.c_void_p(base + 4 * 3 * P), stride, C.c_void_p(base), stride,
                                   _p(ex.views["shs"]), stream)
-    if rc < 0:
-        raise RuntimeError(f"frg_sh_grad_from_views failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_sh_grad_from_views")
 
 
 ROW_FLOATS = 16    # a row of the sparse exchange: index bits, dL_dmeans3D[3], dL_dscales[3], dL_dopacity, dL_drotations[4], dRGB[3], pad
@@ -66,8 +67,7 @@ def _hip_row_packer(ex: "GradientExchange"):
     stream = C.c_void_p(torch.cuda.current_stream(ex.flat.device).cuda_stream)
     rc = _lib.lib().frg_pack_grad_rows(ex.P, _p(v["means3D"]), _p(v["scales"]), _p(v["rotations"]), _p(v["opacities"]),
                                        _p(ex.own_drgb), _p(ex.rows_own), ex.rows_own.shape[0], _p(ex.count_dev), stream)
-    if rc < 0:
-        raise RuntimeError(f"frg_pack_grad_rows failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_pack_grad_rows")
 
 
 def _hip_row_scatterer(ex: "GradientExchange", rows: torch.Tensor, n: int, drgb_dense):
@@ -78,8 +78,7 @@ def _hip_row_scatterer(ex: "GradientExchange", rows: torch.Tensor, n: int, drgb_
     stream = C.c_void_p(torch.cuda.current_stream(ex.flat.device).cuda_stream)
     rc = _lib.lib().frg_scatter_grad_rows(int(n), ex.P, _p(rows), _p(v["means3D"]), _p(v["scales"]), _p(v["rotations"]),
                                           _p(v["opacities"]), _p(drgb_dense), stream)
-    if rc < 0:
-        raise RuntimeError(f"frg_scatter_grad_rows failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_scatter_grad_rows")
 
 
 # ---- the 8-GPU budget -----------------------------------------------------------------------------
@@ -542,8 +541,7 @@ def _hip_sum_packer(ex: "SlotSumExchange", chunk: int, dest: torch.Tensor):
                                       _p(cam.viewmatrix), _p(cam.projmatrix), _p(cam.campos), float(cam.tanfovx), float(cam.tanfovy),
                                       int(cam.image_width), int(cam.image_height), float(c.get("scale_modifier", 1.0)), int(c["D"]),
                                       _p(dest), dest.numel() * 4, int(ex.capacity[chunk]), stream)
-    if rc < 0:
-        raise RuntimeError(f"frg_pack_sum_rows failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_pack_sum_rows")
 
 
 def _hip_sum_combiner(ex: "SlotSumExchange", chunk: int, packets: torch.Tensor, n_views: int, seq: int):
@@ -567,8 +565,7 @@ def _hip_sum_combiner(ex: "SlotSumExchange", chunk: int, packets: torch.Tensor, 
                          dL_dsh=v(g["shs"]), status=v(ex.status[chunk]), status_seq=int(seq), row_live=v(getattr(ex, "row_live", None)),
                          workspace=v(ex.combine_work), workspace_bytes=ex.combine_work.numel(), hip_stream=torch.cuda.current_stream(packets.device).cuda_stream)
     rc = _lib.lib().frg_backward_combine(C.byref(a))
-    if rc < 0:
-        raise RuntimeError(f"frg_backward_combine failed ({rc}): {_lib.last_error()}")
+    _lib.check(rc, "frg_backward_combine")
 
 
 class SlotSumExchange(GradientExchange):
@@ -844,30 +841,6 @@ class DensificationStats:
         self.denom += self._sums[:, 1:2]
 
 
-class _Arena:
-    """Grow-only device buffer handed to the C ABI's allocation callbacks: after
-    the first view no allocator call remains on the per-step path (image size and
-    P are constant per model, only R varies -- SURVEY Appendix A-18)."""
-
-    def __init__(self, device, slack: float = 1.25):
-        self.device, self.slack = device, slack
-        self.buf = torch.empty(0, dtype=torch.uint8, device=device)
-        self.cb = _lib.ALLOC_FN(self._alloc)
-
-    def _alloc(self, _user, nbytes):
-        if self.buf.numel() < nbytes:
-            self.buf = torch.empty(int(nbytes * self.slack) + 256, dtype=torch.uint8, device=self.device)
-        return self.buf.data_ptr()
-
-    def ensure(self, nbytes):
-        self._alloc(None, nbytes)
-        return self.buf
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 class ViewParallelRasterizer:
     """Replicated scene + per-rank view render through the C ABI, gradients written
     in place into the flat exchange buffer (no copies, no zero-fill)."""
@@ -916,7 +889,7 @@ class ViewParallelRasterizer:
         self.dL_dmeans2D, self.dL_dcolors = f(P, 3), f(P, 3)
         self.write_all_outputs = write_all_outputs
         self.dL_dcov3D = f(P, 6) if write_all_outputs else None
-        self.geom, self.binning, self.img, self.work = (_Arena(self.dev) for _ in range(4))
+        self.geom, self.binning, self.img, self.work = (_lib.Scratch(self.dev, 1.25) for _ in range(4))
         self.radii = torch.empty(P, dtype=torch.int32, device=self.dev)
         self.row_live = torch.zeros(P, dtype=torch.uint8, device=self.dev) if live_rows else None
         if live_rows and process_group is not None:
@@ -958,41 +931,28 @@ class ViewParallelRasterizer:
         H, W = cam.image_height, cam.image_width
         if self.out_color is None or tuple(self.out_color.shape) != (3, H, W):
             self.out_color = torch.empty((3, H, W), dtype=torch.float32, device=self.dev)
-        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
         # the blend arithmetic of this forward (the process option, read here) is handed to the backward explicitly: the library
         # then launches that one instantiation instead of both behind the forward's stamp (api.hip backward_impl)
         self._exact = int(_lib.get_option("exact_blend"))
         use_deferred = (self.deferred_counters if deferred is None else deferred) and self.capacity > 0
         if forward_only and use_deferred:
             raise RuntimeError("forward_only is not offered with deferred counters")
-        if keep_mask is not None or self.raw_params or forward_only:
-            v = lambda t: None if t is None else t.data_ptr()
-            rawkw = {}
-            if self.raw_params:
-                rawkw = dict(raw_opacities=v(s.opacities), raw_scales=v(s.scales), raw_rotations=v(s.rotations))
-            a = _lib.ForwardArgs(
-                struct_size=C.sizeof(_lib.ForwardArgs), geometry_alloc=self.geom.cb, binning_alloc=self.binning.cb,
-                image_alloc=self.img.cb, user=None, P=self.P, D=s.sh_degree, M=self.K, background=v(bg), width=W, height=H,
-                means3D=v(s.means3D), shs=v(s.shs), colors_precomp=None, opacities=None if self.raw_params else v(s.opacities),
-                scales=None if self.raw_params else v(s.scales),
-                scale_modifier=1.0, rotations=None if self.raw_params else v(s.rotations), cov3D_precomp=None, viewmatrix=v(cam.viewmatrix),
-                projmatrix=v(cam.projmatrix), cam_pos=v(cam.campos), tan_fovx=float(cam.tanfovx), tan_fovy=float(cam.tanfovy),
-                prefiltered=0, out_color=v(self.out_color), radii=v(self.radii), debug=0, hip_stream=stream.value,
-                instance_capacity=self.capacity if use_deferred else 0, keep_mask=v(keep_mask),
-                forward_only=1 if forward_only else 0, **rawkw)
-            self._keep_alive = keep_mask
+        raw = self.raw_params
+        a = _lib.forward_args(
+            geometry_alloc=self.geom.cb, binning_alloc=self.binning.cb, image_alloc=self.img.cb, P=self.P, D=s.sh_degree, M=self.K,
+            background=bg, width=W, height=H, means3D=s.means3D, shs=s.shs, opacities=None if raw else s.opacities,
+            scales=None if raw else s.scales, scale_modifier=1.0, rotations=None if raw else s.rotations, viewmatrix=cam.viewmatrix,
+            projmatrix=cam.projmatrix, cam_pos=cam.campos, tan_fovx=float(cam.tanfovx), tan_fovy=float(cam.tanfovy),
+            out_color=self.out_color, radii=self.radii, hip_stream=torch.cuda.current_stream(self.dev).cuda_stream,
+            instance_capacity=self.capacity if use_deferred else 0, keep_mask=keep_mask, forward_only=1 if forward_only else 0,
+            raw_opacities=s.opacities if raw else None, raw_scales=s.scales if raw else None, raw_rotations=s.rotations if raw else None)
+        if keep_mask is not None or raw or forward_only:
             rc = L.frg_forward_ex(C.byref(a))
+        elif use_deferred:        # the reference-shaped entry points
+            rc = L.frg_forward_deferred(*_lib.positional(a, _lib.FORWARD_DEFERRED_POSITIONAL))
         else:
-            fn = L.frg_forward_deferred if use_deferred else L.frg_forward
-            rc = fn(self.geom.cb, self.binning.cb, self.img.cb, None,
-                    self.P, s.sh_degree, self.K, _p(bg), W, H,
-                    _p(s.means3D), _p(s.shs), None, _p(s.opacities),
-                    _p(s.scales), 1.0, _p(s.rotations), None,
-                    _p(cam.viewmatrix), _p(cam.projmatrix), _p(cam.campos),
-                    float(cam.tanfovx), float(cam.tanfovy), 0,
-                    _p(self.out_color), _p(self.radii), self.capacity if use_deferred else 0, stream)
-        if rc < 0:
-            raise RuntimeError(f"{'frg_forward_deferred' if use_deferred else 'frg_forward'} failed ({rc}): {_lib.last_error()}")
+            rc = L.frg_forward(*_lib.positional(a, _lib.FORWARD_POSITIONAL))
+        _lib.check(rc, "frg_forward_deferred" if use_deferred else "frg_forward")
         # deferred: rc is the capacity, which is what the backward carves its buffers with
         self.num_rendered = rc
         self._pending = use_deferred and rc > 0
@@ -1015,8 +975,7 @@ class ViewParallelRasterizer:
         if rc == _lib.ECAPACITY:
             self.capacity = int(n.value * self.capacity_slack) + 4096
             return False
-        if rc < 0:
-            raise RuntimeError(f"frg_forward_finish failed ({rc}): {_lib.last_error()}")
+        _lib.check(rc, "frg_forward_finish")
         self.true_num_rendered = n.value
         return True
 
@@ -1061,27 +1020,22 @@ class ViewParallelRasterizer:
         defer_sh = (ex.factor_sh and ex._active()) or slot_sums
         ws = int(L.frg_backward_workspace_bytes(self.P, self.num_rendered))
         work = self.work.ensure(ws)
-        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        stream = _lib.stream_ptr(self.dev)
         # every option of the backward in one struct (frg_backward_ex), the forward's arithmetic stated
-        v = lambda t: None if t is None else t.data_ptr()
         raw = self.raw_params
-        a = _lib.BackwardArgs(
-            struct_size=C.sizeof(_lib.BackwardArgs), P=self.P, D=s.sh_degree, M=self.K, R=self.num_rendered, background=v(bg),
-            width=W, height=H, means3D=v(s.means3D), shs=v(s.shs), colors_precomp=None, scales=None if raw else v(s.scales), scale_modifier=1.0,
-            rotations=None if raw else v(s.rotations), cov3D_precomp=None, viewmatrix=v(cam.viewmatrix), projmatrix=v(cam.projmatrix),
-            campos=v(cam.campos), tan_fovx=float(cam.tanfovx), tan_fovy=float(cam.tanfovy), radii=v(self.radii),
-            geom_buffer=v(self.geom.buf), binning_buffer=v(self.binning.buf), image_buffer=v(self.img.buf),
-            dL_dpix=v(dL_dimage), dL_dmean2D=v(self.dL_dmeans2D), dL_dconic=None, dL_dopacity=v(g["opacities"]),
-            dL_dcolor=v(ex.own_drgb) if defer_sh else (v(self.dL_dcolors) if (ex.factor_sh or self.write_all_outputs) else None),
-            dL_dmean3D=v(g["means3D"]), dL_dcov3D=v(self.dL_dcov3D), dL_dsh=None if defer_sh else v(g["shs"]),
-            dL_dscale=v(g["scales"]), dL_drot=v(g["rotations"]), workspace=v(work), workspace_bytes=work.numel(), debug=0,
-            hip_stream=stream.value, raw_opacities=v(s.opacities) if raw else None, raw_scales=v(s.scales) if raw else None,
-            raw_rotations=v(s.rotations) if raw else None, exact_blend=getattr(self, "_exact", -1) + 1, phase=int(phase),
-            row_live=v(self.row_live), range_first=0 if sum_range is None else int(sum_range[0]),
-            range_count=0 if sum_range is None else int(sum_range[1]))
-        rc = L.frg_backward_ex(C.byref(a))
-        if rc < 0:
-            raise RuntimeError(f"frg_backward failed ({rc}): {_lib.last_error()}")
+        a = _lib.backward_args(
+            P=self.P, D=s.sh_degree, M=self.K, R=self.num_rendered, background=bg, width=W, height=H, means3D=s.means3D, shs=s.shs,
+            scales=None if raw else s.scales, scale_modifier=1.0, rotations=None if raw else s.rotations, viewmatrix=cam.viewmatrix,
+            projmatrix=cam.projmatrix, campos=cam.campos, tan_fovx=float(cam.tanfovx), tan_fovy=float(cam.tanfovy), radii=self.radii,
+            geom_buffer=self.geom.buf, binning_buffer=self.binning.buf, image_buffer=self.img.buf, dL_dpix=dL_dimage,
+            dL_dmean2D=self.dL_dmeans2D, dL_dopacity=g["opacities"],
+            dL_dcolor=ex.own_drgb if defer_sh else (self.dL_dcolors if (ex.factor_sh or self.write_all_outputs) else None),
+            dL_dmean3D=g["means3D"], dL_dcov3D=self.dL_dcov3D, dL_dsh=None if defer_sh else g["shs"], dL_dscale=g["scales"],
+            dL_drot=g["rotations"], workspace=work, workspace_bytes=work.numel(), hip_stream=stream.value,
+            raw_opacities=s.opacities if raw else None, raw_scales=s.scales if raw else None, raw_rotations=s.rotations if raw else None,
+            exact_blend=getattr(self, "_exact", -1) + 1, phase=int(phase), row_live=self.row_live,
+            range_first=0 if sum_range is None else int(sum_range[0]), range_count=0 if sum_range is None else int(sum_range[1]))
+        _lib.check(L.frg_backward_ex(C.byref(a)), "frg_backward")
         if slot_sums:
             gen = self._bwd_gen
             ex.note_view(work=work, R=self.num_rendered, cam=cam, D=s.sh_degree, scale_modifier=1.0,
@@ -1093,8 +1047,7 @@ class ViewParallelRasterizer:
             # this view's share of the factored SH exchange: masked colour gradient + camera centre
             if not defer_sh:   # (with deferred SH rows the backward wrote the payload itself)
                 rc = L.frg_sh_color_grad(self.P, _p(self.geom.buf), _p(self.radii), _p(self.dL_dcolors), _p(ex.own_drgb), stream)
-                if rc < 0:
-                    raise RuntimeError(f"frg_sh_color_grad failed ({rc}): {_lib.last_error()}")
+                _lib.check(rc, "frg_sh_color_grad")
             # 12 bytes, copied every time: a (pointer, version) tag cannot tell a fresh camera tensor that
             # the caching allocator placed at the previous one's address from the previous one
             ex.own_campos.copy_(cam.campos.reshape(-1)[:3], non_blocking=True)

@@ -22,14 +22,6 @@ import torch.nn as nn
 from . import _lib
 
 
-def _ptr(t):
-    """Device pointer of a tensor, or NULL for the reference's 'absent' encoding
-    (empty tensor, DGR/diff_gaussian_rasterization/__init__.py:197-207)."""
-    if t is None or t.numel() == 0:
-        return None
-    return C.c_void_p(t.data_ptr())
-
-
 def _f32c(t, device):
     if t is None or t.numel() == 0:
         return None
@@ -38,30 +30,6 @@ def _f32c(t, device):
     if t.device != device:
         raise RuntimeError(f"tensor on {t.device}, expected {device}")
     return t.contiguous()
-
-
-def _stream_ptr(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-class _Buffers:
-    """The three resizable scratch tensors of the reference binding
-    (rasterize_points.cu:27-33,71-78), grown through the C-ABI callbacks."""
-
-    def __init__(self, device):
-        self.device = device
-        self.geom = torch.empty(0, dtype=torch.uint8, device=device)
-        self.binning = torch.empty(0, dtype=torch.uint8, device=device)
-        self.img = torch.empty(0, dtype=torch.uint8, device=device)
-
-        def make(name):
-            def cb(_user, nbytes):
-                t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.device)
-                setattr(self, name, t)
-                return t.data_ptr()
-            return _lib.ALLOC_FN(cb)
-
-        self.cb_geom, self.cb_binning, self.cb_img = make("geom"), make("binning"), make("img")
 
 
 class _NativeOps:
@@ -88,43 +56,26 @@ class _NativeOps:
         with torch.cuda.device(dev):
             out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
             radii = torch.empty((P,), dtype=torch.int32, device=dev)
-            bufs = _Buffers(dev)
+            geom, binning, img = (_lib.Scratch(dev) for _ in range(3))
             M = int(sh.shape[1]) if sh is not None and sh.numel() != 0 else 0
-            t = dict(bg=_f32c(background, dev), means=_f32c(means3D, dev), colors=_f32c(colors, dev),
-                     opac=_f32c(opacity, dev), scales=_f32c(scales, dev), rots=_f32c(rotations, dev),
-                     cov=_f32c(cov3D_precomp, dev), view=_f32c(viewmatrix, dev), proj=_f32c(projmatrix, dev),
-                     sh=_f32c(sh, dev), campos=_f32c(campos, dev))
-            if keep_mask is None and modes is None:
-                rc = L.frg_forward(bufs.cb_geom, bufs.cb_binning, bufs.cb_img, None,
-                                   P, int(degree), M, _ptr(t["bg"]), W, H,
-                                   _ptr(t["means"]), _ptr(t["sh"]), _ptr(t["colors"]), _ptr(t["opac"]),
-                                   _ptr(t["scales"]), float(scale_modifier), _ptr(t["rots"]), _ptr(t["cov"]),
-                                   _ptr(t["view"]), _ptr(t["proj"]), _ptr(t["campos"]),
-                                   float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
-                                   _ptr(out_color), _ptr(radii) if P else None, int(bool(debug)), _stream_ptr(dev))
+            if keep_mask is not None and (keep_mask.shape != (P,) or keep_mask.device != dev or
+                                          keep_mask.dtype not in (torch.bool, torch.uint8)):
+                raise RuntimeError("keep_mask must be a bool / uint8 tensor of shape (num_points,) on the Gaussians' device")
+            a = _lib.forward_args(
+                geometry_alloc=geom.cb, binning_alloc=binning.cb, image_alloc=img.cb, P=P, D=int(degree), M=M,
+                background=_f32c(background, dev), width=W, height=H, means3D=_f32c(means3D, dev), shs=_f32c(sh, dev),
+                colors_precomp=_f32c(colors, dev), opacities=_f32c(opacity, dev), scales=_f32c(scales, dev),
+                scale_modifier=float(scale_modifier), rotations=_f32c(rotations, dev), cov3D_precomp=_f32c(cov3D_precomp, dev),
+                viewmatrix=_f32c(viewmatrix, dev), projmatrix=_f32c(projmatrix, dev), cam_pos=_f32c(campos, dev),
+                tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), prefiltered=int(bool(prefiltered)), out_color=out_color,
+                radii=radii, debug=int(bool(debug)), hip_stream=torch.cuda.current_stream(dev).cuda_stream,
+                keep_mask=None if keep_mask is None else keep_mask.contiguous(), modes=modes)
+            if keep_mask is None and modes is None:      # the reference-shaped entry point (rasterizer.h:33-56)
+                rc = L.frg_forward(*_lib.positional(a, _lib.FORWARD_POSITIONAL))
             else:
-                if keep_mask is not None and (keep_mask.shape != (P,) or keep_mask.device != dev or
-                                              keep_mask.dtype not in (torch.bool, torch.uint8)):
-                    raise RuntimeError("keep_mask must be a bool / uint8 tensor of shape (num_points,) on the Gaussians' device")
-                mask = None if keep_mask is None else keep_mask.contiguous()
-
-                def vp(x):
-                    return None if x is None else x.value
-                a = _lib.ForwardArgs(
-                    struct_size=C.sizeof(_lib.ForwardArgs), geometry_alloc=bufs.cb_geom, binning_alloc=bufs.cb_binning,
-                    image_alloc=bufs.cb_img, user=None, P=P, D=int(degree), M=M, background=vp(_ptr(t["bg"])), width=W,
-                    height=H, means3D=vp(_ptr(t["means"])), shs=vp(_ptr(t["sh"])), colors_precomp=vp(_ptr(t["colors"])),
-                    opacities=vp(_ptr(t["opac"])), scales=vp(_ptr(t["scales"])), scale_modifier=float(scale_modifier),
-                    rotations=vp(_ptr(t["rots"])), cov3D_precomp=vp(_ptr(t["cov"])), viewmatrix=vp(_ptr(t["view"])),
-                    projmatrix=vp(_ptr(t["proj"])), cam_pos=vp(_ptr(t["campos"])), tan_fovx=float(tan_fovx),
-                    tan_fovy=float(tan_fovy), prefiltered=int(bool(prefiltered)), out_color=out_color.data_ptr(),
-                    radii=radii.data_ptr() if P else None, debug=int(bool(debug)), hip_stream=_stream_ptr(dev).value,
-                    instance_capacity=0, keep_mask=mask.data_ptr() if (P and mask is not None) else None,
-                    **_lib.mode_fields(modes))
                 rc = L.frg_forward_ex(C.byref(a))
-        if rc < 0:
-            raise RuntimeError(f"frg_forward failed ({rc}): {_lib.last_error()}")
-        return rc, out_color, radii, bufs.geom, bufs.binning, bufs.img
+        _lib.check(rc, "frg_forward")
+        return rc, out_color, radii, geom.buf, binning.buf, img.buf
 
     @staticmethod
     def rasterize_gaussians_masked(*args):
@@ -184,39 +135,22 @@ class _NativeOps:
             if P != 0:
                 ws_bytes = int(L.frg_backward_workspace_bytes(P, int(R)))
                 workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-                t = dict(bg=_f32c(background, dev), means=_f32c(means3D, dev), colors=_f32c(colors, dev),
-                         scales=_f32c(scales, dev), rots=_f32c(rotations, dev), cov=_f32c(cov3D_precomp, dev),
-                         view=_f32c(viewmatrix, dev), proj=_f32c(projmatrix, dev), sh=_f32c(sh, dev),
-                         campos=_f32c(campos, dev), dpix=_f32c(dL_dout_color, dev), radii=radii.contiguous())
+                a = _lib.backward_args(
+                    P=P, D=int(degree), M=M, R=int(R), background=_f32c(background, dev), width=W, height=H,
+                    means3D=_f32c(means3D, dev), shs=_f32c(sh, dev), colors_precomp=_f32c(colors, dev), scales=_f32c(scales, dev),
+                    scale_modifier=float(scale_modifier), rotations=_f32c(rotations, dev), cov3D_precomp=_f32c(cov3D_precomp, dev),
+                    viewmatrix=_f32c(viewmatrix, dev), projmatrix=_f32c(projmatrix, dev), campos=_f32c(campos, dev),
+                    tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), radii=radii.contiguous(), geom_buffer=geomBuffer,
+                    binning_buffer=binningBuffer, image_buffer=imageBuffer, dL_dpix=_f32c(dL_dout_color, dev),
+                    dL_dmean2D=dL_dmeans2D, dL_dopacity=dL_dopacity, dL_dcolor=dL_dcolors, dL_dmean3D=dL_dmeans3D,
+                    dL_dcov3D=dL_dcov3D, dL_dsh=dL_dsh if has_sh else None, dL_dscale=dL_dscales if has_sr else None,
+                    dL_drot=dL_drotations if has_sr else None, workspace=workspace, workspace_bytes=ws_bytes,
+                    debug=int(bool(debug)), hip_stream=torch.cuda.current_stream(dev).cuda_stream, exact_blend=int(exact_blend) + 1)
                 if int(exact_blend) < 0:      # the reference-shaped entry point (rasterizer.h:58-84)
-                    rc = L.frg_backward(P, int(degree), M, int(R), _ptr(t["bg"]), W, H,
-                                        _ptr(t["means"]), _ptr(t["sh"]), _ptr(t["colors"]),
-                                        _ptr(t["scales"]), float(scale_modifier), _ptr(t["rots"]), _ptr(t["cov"]),
-                                        _ptr(t["view"]), _ptr(t["proj"]), _ptr(t["campos"]),
-                                        float(tan_fovx), float(tan_fovy), _ptr(t["radii"]),
-                                        _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(t["dpix"]),
-                                        _ptr(dL_dmeans2D), None, _ptr(dL_dopacity), _ptr(dL_dcolors),
-                                        _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dsh) if has_sh else None,
-                                        _ptr(dL_dscales) if has_sr else None, _ptr(dL_drotations) if has_sr else None,
-                                        _ptr(workspace), ws_bytes, int(bool(debug)), _stream_ptr(dev))
+                    rc = L.frg_backward(*_lib.positional(a, _lib.BACKWARD_POSITIONAL))
                 else:
-                    def vp(x):
-                        return None if x is None else x.value
-                    a = _lib.BackwardArgs(
-                        struct_size=C.sizeof(_lib.BackwardArgs), P=P, D=int(degree), M=M, R=int(R), background=vp(_ptr(t["bg"])),
-                        width=W, height=H, means3D=vp(_ptr(t["means"])), shs=vp(_ptr(t["sh"])), colors_precomp=vp(_ptr(t["colors"])),
-                        scales=vp(_ptr(t["scales"])), scale_modifier=float(scale_modifier), rotations=vp(_ptr(t["rots"])),
-                        cov3D_precomp=vp(_ptr(t["cov"])), viewmatrix=vp(_ptr(t["view"])), projmatrix=vp(_ptr(t["proj"])),
-                        campos=vp(_ptr(t["campos"])), tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), radii=vp(_ptr(t["radii"])),
-                        geom_buffer=vp(_ptr(geomBuffer)), binning_buffer=vp(_ptr(binningBuffer)), image_buffer=vp(_ptr(imageBuffer)),
-                        dL_dpix=vp(_ptr(t["dpix"])), dL_dmean2D=vp(_ptr(dL_dmeans2D)), dL_dconic=None, dL_dopacity=vp(_ptr(dL_dopacity)),
-                        dL_dcolor=vp(_ptr(dL_dcolors)), dL_dmean3D=vp(_ptr(dL_dmeans3D)), dL_dcov3D=vp(_ptr(dL_dcov3D)),
-                        dL_dsh=vp(_ptr(dL_dsh)) if has_sh else None, dL_dscale=vp(_ptr(dL_dscales)) if has_sr else None,
-                        dL_drot=vp(_ptr(dL_drotations)) if has_sr else None, workspace=vp(_ptr(workspace)), workspace_bytes=ws_bytes,
-                        debug=int(bool(debug)), hip_stream=_stream_ptr(dev).value, exact_blend=int(exact_blend) + 1)
                     rc = L.frg_backward_ex(C.byref(a))
-                if rc < 0:
-                    raise RuntimeError(f"frg_backward failed ({rc}): {_lib.last_error()}")
+                _lib.check(rc, "frg_backward")
                 # keep the workspace alive until the stream has consumed it
                 workspace.record_stream(torch.cuda.current_stream(dev))
         return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
@@ -230,9 +164,8 @@ class _NativeOps:
         if P != 0:
             with torch.cuda.device(dev):
                 m, v, p = _f32c(means3D, dev), _f32c(viewmatrix, dev), _f32c(projmatrix, dev)
-                rc = L.frg_mark_visible(P, _ptr(m), _ptr(v), _ptr(p), _ptr(present), _stream_ptr(dev))
-            if rc < 0:
-                raise RuntimeError(f"frg_mark_visible failed ({rc}): {_lib.last_error()}")
+                _lib.check(L.frg_mark_visible(P, _lib.ptr(m), _lib.ptr(v), _lib.ptr(p), _lib.ptr(present), _lib.stream_ptr(dev)),
+                           "frg_mark_visible")
         return present
 
 

@@ -229,9 +229,11 @@ typedef struct frg_backward_args {
     float *dL_dshell_logits, *dL_dshell_cell_verts;
     /* second generation (struct_size tells): exact_blend 1 | 2 = fast | exact arithmetic of THIS backward's blend
      * pass; 0 (and frg_backward, which has no such argument) = the arithmetic of the forward that filled the buffers --
-     * per-call mode or process default at the time of THAT call: the library remembers it for the 1024 most recent
-     * geometry buffers of the process, and for a buffer it does not know (cloned, restored at another address, older) it
-     * reads the word the forward's blend kernel stamped into image_buffer (one blocking 4-byte copy on hip_stream).
+     * per-call mode or process default at the time of THAT call, which the forward's blend kernel stamped into
+     * image_buffer: BOTH instantiations of the backward blend are launched and each leaves at once unless the stamp names
+     * it.  The library remembers the 1024 most recent geometry buffers of the process; for a buffer it does not know
+     * (cloned, restored at another address, older) the call additionally copies the forward's counters (48 bytes) to the
+     * host and waits for hip_stream -- a host synchronisation per backward -- and then launches the one the stamp names.
      * frg_set_option's value at the time of the backward plays no part.  A caller that carries the forward's mode beside
      * the buffers (the autograd ctx of frosting_amd/rasterizer.py does) states it here and saves that lookup.
      * shell_bary_mode as in frg_forward_args, and equal to the forward's */

@@ -243,3 +243,50 @@ def test_sum_packet_size_formula():
     for n, cap in ((1, 0), (64, 64), (65, 7), (1000, 1000), (1_500_000, 204_800), (3_000_000, 3_000_000)):
         assert 4 * sum_packet_words(n, cap) == L.frg_sum_packet_bytes(n, cap), (n, cap)
     assert sum_packet_words(1_500_000, 204_800) * 4 < 0.15 * 1_500_000 * 48 + 400_000
+
+
+def test_scratch_chunk_and_argument_records_are_freed_by_reference_counting():
+    """The scratch chunk's callback holds the tensor's holder, not the chunk (no cycle): the chunk and its memory go with the
+    last reference, not with the next run of the cyclic collector.  A struct from forward_args / backward_args keeps the
+    tensors it points into alive exactly as long as it lives, and rejects names the C struct does not have."""
+    import ctypes as C
+    import gc
+    import weakref
+    from frosting_amd.parallel import _Arena
+    assert _Arena is _lib.Scratch
+    gc.collect()
+    gc.disable()
+    try:
+        chunk = _lib.Scratch("cpu", 1.25)
+        # (plain booleans in the asserts: pytest's rewritten asserts would hold the objects they look at)
+        driven = chunk.cb(None, 1000) == chunk.buf.data_ptr() and chunk.buf.numel() >= 1000 and chunk.ensure(500) is chunk.buf
+        assert driven
+        refs = weakref.ref(chunk), weakref.ref(chunk.buf)
+        del chunk
+        dead = [r() is None for r in refs]
+        assert dead == [True, True]
+
+        chunk, t, out = _lib.Scratch("cpu"), torch.zeros(7), torch.zeros(3, 8, 8)
+        a = _lib.forward_args(geometry_alloc=chunk.cb, P=7, means3D=t, out_color=out, shs=torch.Tensor([]), opacities=None,
+                              modes={"exact_blend": 1})
+        assert a.struct_size == C.sizeof(_lib.ForwardArgs) and a.means3D == t.data_ptr() and a.out_color == out.data_ptr()
+        assert a.shs is None and a.opacities is None and (a.exact_blend, a.forward_only) == (2, 0)
+        assert _lib.positional(a, _lib.FORWARD_POSITIONAL)[4:7] == [7, 0, 0] and len(_lib.FORWARD_POSITIONAL) == 28
+        b = _lib.backward_args(P=7, means3D=t, exact_blend=1)
+        assert b.struct_size == C.sizeof(_lib.BackwardArgs) and b.means3D == t.data_ptr() and len(_lib.BACKWARD_POSITIONAL) == 37
+        refs = weakref.ref(t), weakref.ref(out), weakref.ref(chunk)
+        del t, out, chunk
+        alive = [r() is not None for r in refs]               # the structs hold them
+        assert alive == [True, True, False]                   # (the chunk itself is not needed: its callback holds the memory)
+        del b
+        alive = [r() is not None for r in refs]
+        assert alive == [True, True, False]
+        del a
+        alive = [r() is not None for r in refs]
+        assert alive == [False, False, False]
+    finally:
+        gc.enable()
+    with pytest.raises(TypeError, match="no_such_field"):
+        _lib.forward_args(P=1, no_such_field=2)
+    with pytest.raises(KeyError):
+        _lib.forward_args(modes={"no_such_mode": 1})
