@@ -16,7 +16,18 @@
 #include <chrono>
 #include <initializer_list>
 #include <mutex>
+#include <optional>
 #include <thread>
+
+// the options the launchers read (declared in kernels.h)
+namespace frg {
+std::atomic<int> g_rows_grid{0};
+std::atomic<int> g_sort_heavy_on_caller{1};
+std::atomic<int> g_fwd_prefetch{1};
+std::atomic<int> g_fwd_order{1};
+std::atomic<int> g_bwd_waves{0};
+std::atomic<int> g_combine_blocks{0};   // 3, 6, 12 or 24 are the useful values; same results
+}  // namespace frg
 
 namespace {
 
@@ -222,69 +233,64 @@ std::atomic<int> g_clear_image_state{0};   // 1: the memset in front of every fo
 // told that no backward follows.  Scheduling hints and early refusals only -- keyed by ADDRESS, a note can be stale (a buffer
 // copied to an address an earlier forward used), so nothing that decides a gradient bit hangs on one: the blend arithmetic
 // and "nothing kept" are stamped into the image chunk by the forward's blend kernel (Counters::fwd_flags) and read there
-// (backward_impl).  A ring of kFwdNotes entries; a forgotten forward's backward launches both forms of the per-Gaussian
-// backward (as if nothing had been posted).  The pinned mailboxes are never freed.
-struct FwdNote { const void* geom = nullptr; const frg::Mailbox* mail = nullptr; uint32_t seq = 0; int exact = -1; int rendered = -1; bool fwd_only = false; };
-constexpr int kFwdNotes = 1024;
+// (backward_impl).  A ring of kFwdNotes entries (the entry of the same address is overwritten, else the next ring slot); a
+// forgotten forward's note reads "unknown" everywhere (rendered -1, forward_only settled by the stamp, both forms of the
+// per-Gaussian backward launched as if nothing had been posted).  The pinned mailboxes are never freed.
+struct FwdNote {
+    const void* geom = nullptr; const frg::Mailbox* mail = nullptr; uint32_t seq = 0; int exact = -1; int rendered = -1; bool fwd_only = false;
+    // -> the number of heavy waves the forward's scatter posted, or -1 when unknown (no post, not arrived yet, the mailbox
+    // already belongs to a later forward)
+    int heavy_waves_posted() const
+    {
+        if (!mail || !g_use_mailbox.load(std::memory_order_relaxed)) return -1;
+        // The forward returned when the scan stage was through; the scatter posts as its first act.  A backward called
+        // straight away may be a few microseconds early: it waits that long (the GPU has the rest of the forward ahead of
+        // it, the host nothing better to do), but not for a scatter stuck behind other work.
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned spin = 0;; spin++) {
+            const unsigned long long post = __atomic_load_n(&mail->heavy_post, __ATOMIC_ACQUIRE);    // (sequence << 32) | count, one word
+            const uint32_t cur = (uint32_t)(post >> 32);
+            if (cur == seq) return (int)((uint32_t)post > 0x7fffffffu ? 0x7fffffffu : (uint32_t)post);
+            if ((int32_t)(cur - seq) > 0) return -1;      // the mailbox already carries a later forward's post
+            if ((spin & 63u) == 63u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(40)) return -1;
+            cpu_relax();
+        }
+    }
+};
 std::mutex g_heavy_mu;
-FwdNote g_fwd_notes[kFwdNotes];
-unsigned g_fwd_next = 0;
-// a forward starts on `geom`: whatever an earlier forward posted about this buffer is void now
-void note_forward(const void* geom, int exact, bool fwd_only)
-{
-    std::lock_guard<std::mutex> lk(g_heavy_mu);
-    for (auto& n : g_fwd_notes) if (n.geom == geom) { n.mail = nullptr; n.seq = 0; n.exact = exact; n.rendered = -1; n.fwd_only = fwd_only; return; }
-    g_fwd_notes[g_fwd_next++ % kFwdNotes] = FwdNote{geom, nullptr, 0, exact, -1, fwd_only};
-}
-// the forward that last filled `geom` was told that no backward would follow (frg_forward_args::forward_only): 1 | 0, or
-// -1 when that forward is not remembered
-int forward_was_forward_only(const void* geom)
-{
-    std::lock_guard<std::mutex> lk(g_heavy_mu);
-    for (const auto& n : g_fwd_notes) if (n.geom == geom) return n.fwd_only ? 1 : 0;
-    return -1;
-}
-// the blocking forward on `geom` rendered R instances (a deferred forward does not know)
-void note_rendered(const void* geom, int R)
-{
-    std::lock_guard<std::mutex> lk(g_heavy_mu);
-    for (auto& n : g_fwd_notes) if (n.geom == geom) { n.rendered = R; return; }
-}
-// -> the instance count of the forward that last filled `geom`, or -1 when it is not remembered
-int forward_rendered(const void* geom)
-{
-    std::lock_guard<std::mutex> lk(g_heavy_mu);
-    for (const auto& n : g_fwd_notes) if (n.geom == geom) return n.rendered;
-    return -1;
-}
-void note_heavy_post(const void* geom, const frg::Mailbox* mail, uint32_t seq)
-{
-    std::lock_guard<std::mutex> lk(g_heavy_mu);
-    for (auto& n : g_fwd_notes) if (n.geom == geom) { n.mail = mail; n.seq = seq; return; }
-}
-// -> the number of heavy waves of the forward that last filled `geom`, or -1 when unknown (no post, not arrived yet,
-// the mailbox already belongs to a later forward)
-int heavy_waves_posted(const void* geom)
-{
-    FwdNote n;
+class FwdNotes {
+    static constexpr int kFwdNotes = 1024;
+    FwdNote ring[kFwdNotes];
+    unsigned next = 0;
+    FwdNote* locate(const void* geom)
+    {
+        for (auto& n : ring) if (n.geom == geom) return &n;
+        return nullptr;
+    }
+public:
+    // a forward starts on `geom`: whatever an earlier forward posted about this buffer is void now
+    void begin(const void* geom, int exact, bool fwd_only)
     {
         std::lock_guard<std::mutex> lk(g_heavy_mu);
-        for (const auto& x : g_fwd_notes) if (x.geom == geom) n = x;
+        FwdNote* n = locate(geom);
+        *(n ? n : &ring[next++ % kFwdNotes]) = FwdNote{geom, nullptr, 0, exact, -1, fwd_only};
     }
-    if (!n.mail || !g_use_mailbox.load(std::memory_order_relaxed)) return -1;
-    // The forward returned when the scan stage was through; the scatter posts as its first act.  A backward called
-    // straight away may be a few microseconds early: it waits that long (the GPU has the rest of the forward ahead of
-    // it, the host nothing better to do), but not for a scatter stuck behind other work.
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spin = 0;; spin++) {
-        const unsigned long long post = __atomic_load_n(&n.mail->heavy_post, __ATOMIC_ACQUIRE);    // (sequence << 32) | count, one word
-        const uint32_t cur = (uint32_t)(post >> 32);
-        if (cur == n.seq) return (int)((uint32_t)post > 0x7fffffffu ? 0x7fffffffu : (uint32_t)post);
-        if ((int32_t)(cur - n.seq) > 0) return -1;      // the mailbox already carries a later forward's post
-        if ((spin & 63u) == 63u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(40)) return -1;
-        cpu_relax();
+    // the forward on `geom` learnt something (its instance count, its scatter's mailbox post); a forgotten forward learns nothing
+    template <class Fn>
+    void update(const void* geom, Fn fn)
+    {
+        std::lock_guard<std::mutex> lk(g_heavy_mu);
+        if (FwdNote* n = locate(geom)) fn(*n);
     }
-}
+    // -> a copy of the note of the forward that last filled `geom`; nothing when that forward is not remembered
+    std::optional<FwdNote> find(const void* geom)
+    {
+        std::lock_guard<std::mutex> lk(g_heavy_mu);
+        const FwdNote* n = locate(geom);
+        return n ? std::optional<FwdNote>(*n) : std::nullopt;
+    }
+};
+FwdNotes g_fwd_notes;
 
 // Two-call backward (frg_backward_args::phase): phase 2 reads the nine per-Gaussian sums phase 1 left in the workspace.
 // What phase 1 was called with is remembered per workspace pointer; a phase 2 that does not match (an arena that grew or
@@ -328,74 +334,24 @@ bool mailbox_wait(const uint32_t* flag, uint32_t seq, hipStream_t stream)
     }
 }
 
-// Side stream of the deferred SH colour kernel (one per host thread and device, like the sort's).
-struct ShSide {
-    hipStream_t stream = nullptr;
-    hipEvent_t geo_done = nullptr, sh_done = nullptr;
-    int device = -1;
-    bool ensure()
-    {
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess) return false;
-        if (dev == device) return true;
-        if (stream) (void)hipStreamDestroy(stream);
-        if (geo_done) (void)hipEventDestroy(geo_done);
-        if (sh_done) (void)hipEventDestroy(sh_done);
-        stream = nullptr; geo_done = nullptr; sh_done = nullptr; device = -1;
-        // lowest priority: the colour kernel floods every CU with streaming waves; the small latency-bound kernels
-        // of the binning stages on the caller's stream must win the arbitration
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, least) != hipSuccess) return false;
-        if (hipEventCreateWithFlags(&geo_done, hipEventDisableTiming) != hipSuccess) return false;
-        if (hipEventCreateWithFlags(&sh_done, hipEventDisableTiming) != hipSuccess) return false;
-        device = dev;
-        return true;
-    }
-};
-thread_local ShSide g_sh_side;
+// Side streams (frg::SideStream, kernels.h), one per host thread each:
+// the deferred SH colour kernel's (fork: the geometry is there | join: the colours are).  Lowest priority: the colour
+// kernel floods every CU with streaming waves; the small latency-bound kernels of the binning stages on the caller's
+// stream must win the arbitration
+thread_local frg::SideStream g_sh_side{frg::SideStream::LOWEST};
+// the timing experiments' ("probe")
+thread_local frg::SideStream g_probe_side{frg::SideStream::DEFAULT};
+// the per-Gaussian backward's 16-wave launch's.  HIGHEST priority: the 16-wave workgroups need a whole CU's LDS each; both
+// launches become ready when the blend backward ends, and unless the dispatcher places these first they wait until the
+// plain kernel has drained (rocprofv3, round 3: 274 us "duration" for a launch whose workgroups found an empty list)
+thread_local frg::SideStream g_bwd_side{frg::SideStream::HIGHEST};
 
-struct ProbeSide {
-    hipStream_t stream = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    bool ensure()
-    {
-        if (stream) return true;
-        if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return false;
-        if (hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess) return false;
-        if (hipEventCreateWithFlags(&join, hipEventDisableTiming) != hipSuccess) return false;
-        return true;
-    }
-};
-thread_local ProbeSide g_probe_side;
-// side stream of the per-Gaussian backward's 16-wave launch (one per host thread, re-created when the thread's
-// current device changes)
-struct BwdSide {
-    hipStream_t stream = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    int device = -1;
-    bool ensure()
-    {
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess) return false;
-        if (dev == device) return true;
-        if (stream) (void)hipStreamDestroy(stream);
-        if (fork) (void)hipEventDestroy(fork);
-        if (join) (void)hipEventDestroy(join);
-        stream = nullptr; fork = nullptr; join = nullptr; device = -1;
-        // HIGHEST priority: the 16-wave workgroups need a whole CU's LDS each; both launches become ready when the blend
-        // backward ends, and unless the dispatcher places these first they wait until the plain kernel has drained
-        // (rocprofv3, round 3: 274 us "duration" for a launch whose workgroups found an empty list)
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, greatest) != hipSuccess) return false;
-        if (hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess) return false;
-        if (hipEventCreateWithFlags(&join, hipEventDisableTiming) != hipSuccess) return false;
-        device = dev;
-        return true;
-    }
-};
-thread_local BwdSide g_bwd_side;
+// a negative return code leaves the function
+#define FRG_TRY(expr)                  \
+    do {                               \
+        const int rc_ = (expr);        \
+        if (rc_ < 0) return rc_;       \
+    } while (0)
 
 #define FRG_HIP(call)                                                                              \
     do {                                                                                           \
@@ -452,6 +408,49 @@ bool widen(const Args* a, std::initializer_list<size_t> generations, Args* full)
     return true;
 }
 
+// Every option of frg_set_option / frg_get_option: its name, where its value lives, what is stored for a requested value.
+// Experiment knobs ("ablate" and "probe" make kernels skip work or ignore dependencies: WRONG results) can be set only in a
+// process started with FROSTING_EXPERIMENTS=1, so that a stray call cannot switch them on, and do not answer frg_get_option.
+struct Option {
+    const char* name;
+    std::atomic<int>* value;
+    int (*stored)(int requested);
+    bool experiment;
+};
+int as_flag(int v) { return v ? 1 : 0; }
+int not_negative(int v) { return v < 0 ? 0 : v; }
+const Option kOptions[] = {
+    {"exact_blend", &g_exact_blend, as_flag, false},     // (unset until first asked for: FROSTING_EXACT_BLEND, exact_blend())
+    {"profile", &g_profile, as_flag, false},
+    {"profile_stage", &g_profile_stage, [](int v) { return v < 0 || v >= ST_COUNT ? -1 : v; }, false},
+    {"global_bins", &g_global_bins, as_flag, false},
+    {"tight_binning", &g_tight_binning, as_flag, false},
+    {"bwd_batch", &g_bwd_batch, [](int v) { return v == 2 ? 2 : 3; }, false},
+    {"bwd_seg_log", &g_bwd_seg_log, [](int v) { return v >= FRG_BWD_SEG_LOG_MIN && v <= FRG_BWD_SEG_LOG_MAX ? v : 0; }, false},
+    {"counter_mailbox", &g_use_mailbox, as_flag, false},
+    {"sparse_sh", &g_sparse_sh, as_flag, false},
+    {"fwd_prefetch", &frg::g_fwd_prefetch, as_flag, false},
+    {"bwd_heavy_first", &g_bwd_heavy_first, as_flag, false},
+    {"bwd_waves", &frg::g_bwd_waves, not_negative, false},
+    {"fwd_order", &frg::g_fwd_order, as_flag, false},
+    {"sh_dir_in_backward", &g_sh_no_dir, as_flag, false},
+    {"clear_image_state", &g_clear_image_state, as_flag, false},
+    {"sort_heavy_on_caller", &frg::g_sort_heavy_on_caller, as_flag, false},
+    {"async_sh", &g_async_sh, [](int v) { return v < 0 || v > 3 ? 1 : v; }, false},
+    {"fused_small", &g_fused_small, as_flag, false},
+    {"fwd_unroll8", &g_fwd_unroll8, [](int v) { return v < 0 || v > 2 ? 1 : v; }, false},
+    {"combine_blocks", &frg::g_combine_blocks, not_negative, false},
+    {"ablate", &g_ablate, [](int v) { return v; }, true},
+    {"probe", &g_probe, [](int v) { return v; }, true},
+    {"assume_no_heavy", &g_assume_no_heavy, as_flag, true},
+    {"rows_grid", &frg::g_rows_grid, [](int v) { return v <= 0 ? 0 : v < 8 ? 8 : v; }, true},
+};
+const Option* find_option(const char* name)
+{
+    for (const Option& o : kOptions) if (name && strcmp(name, o.name) == 0) return &o;
+    return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -461,44 +460,16 @@ const char* frg_last_error(void) { return g_err; }
 
 int frg_set_option(const char* name, int value)
 {
-    if (name && strcmp(name, "exact_blend") == 0) {
-        int old = exact_blend();
-        g_exact_blend.store(value ? 1 : 0);
-        return old;
-    }
-    if (name && strcmp(name, "profile") == 0) return g_profile.exchange(value ? 1 : 0);
-    if (name && strcmp(name, "profile_stage") == 0) return g_profile_stage.exchange(value < 0 || value >= ST_COUNT ? -1 : value);
-    if (name && strcmp(name, "global_bins") == 0) return g_global_bins.exchange(value ? 1 : 0);
-    if (name && strcmp(name, "tight_binning") == 0) return g_tight_binning.exchange(value ? 1 : 0);
-    if (name && strcmp(name, "bwd_batch") == 0) return g_bwd_batch.exchange(value == 2 ? 2 : 3);
-    if (name && strcmp(name, "bwd_seg_log") == 0) return g_bwd_seg_log.exchange(value >= FRG_BWD_SEG_LOG_MIN && value <= FRG_BWD_SEG_LOG_MAX ? value : 0);
-    if (name && strcmp(name, "counter_mailbox") == 0) return g_use_mailbox.exchange(value ? 1 : 0);
-    if (name && strcmp(name, "sparse_sh") == 0) return g_sparse_sh.exchange(value ? 1 : 0);
-    if (name && strcmp(name, "fwd_prefetch") == 0) { const int old = frg::g_fwd_prefetch; frg::g_fwd_prefetch = value ? 1 : 0; return old; }
-    if (name && strcmp(name, "bwd_heavy_first") == 0) return g_bwd_heavy_first.exchange(value ? 1 : 0);
-    if (name && strcmp(name, "bwd_waves") == 0) { const int old = frg::g_bwd_waves; frg::g_bwd_waves = value < 0 ? 0 : value; return old; }
-    if (name && strcmp(name, "fwd_order") == 0) { const int old = frg::g_fwd_order; frg::g_fwd_order = value ? 1 : 0; return old; }
-    if (name && strcmp(name, "sh_dir_in_backward") == 0) return g_sh_no_dir.exchange(value ? 1 : 0);
-    if (name && strcmp(name, "clear_image_state") == 0) return g_clear_image_state.exchange(value ? 1 : 0);
-    if (name && strcmp(name, "sort_heavy_on_caller") == 0) { const int old = frg::g_sort_heavy_on_caller; frg::g_sort_heavy_on_caller = value ? 1 : 0; return old; }
-    // timing-experiment knobs: "ablate" and "probe" make kernels skip work or ignore dependencies (WRONG results), so a
-    // stray call must not be able to switch them on -- they exist only in processes started with FROSTING_EXPERIMENTS=1
-    if (name && (strcmp(name, "ablate") == 0 || strcmp(name, "probe") == 0 || strcmp(name, "rows_grid") == 0 || strcmp(name, "assume_no_heavy") == 0)) {
+    const Option* o = find_option(name);
+    if (!o) return fail(FRG_EINVAL, "unknown option '%s'", name ? name : "(null)");
+    if (o->experiment) {
         static const bool experiments = [] { const char* e = getenv("FROSTING_EXPERIMENTS"); return e && e[0] == '1'; }();
         if (!experiments)
             return fail(FRG_EINVAL, "option '%s' is a timing experiment (results are wrong by design): start the process with "
                                     "FROSTING_EXPERIMENTS=1 to use it", name);
-        if (strcmp(name, "ablate") == 0) return g_ablate.exchange(value);
-        if (strcmp(name, "probe") == 0) return g_probe.exchange(value);
-        if (strcmp(name, "assume_no_heavy") == 0) return g_assume_no_heavy.exchange(value ? 1 : 0);
-        const int old = frg::g_rows_grid; frg::g_rows_grid = value <= 0 ? 0 : value < 8 ? 8 : value; return old;
     }
-    if (name && strcmp(name, "async_sh") == 0) return g_async_sh.exchange(value < 0 || value > 3 ? 1 : value);
-    if (name && strcmp(name, "fused_small") == 0) return g_fused_small.exchange(value ? 1 : 0);
-    if (name && strcmp(name, "fwd_unroll8") == 0) return g_fwd_unroll8.exchange(value < 0 || value > 2 ? 1 : value);
-    // tuning: blocks of 64 Gaussians per tile of the combine pass (3, 6, 12 or 24; 0 = chosen from the number of views); same results
-    if (name && strcmp(name, "combine_blocks") == 0) { const int old = frg::g_combine_blocks; frg::g_combine_blocks = value < 0 ? 0 : value; return old; }
-    return fail(FRG_EINVAL, "unknown option '%s'", name ? name : "(null)");
+    if (o->value == &g_exact_blend) (void)exact_blend();      // the previous value is the resolved one
+    return o->value->exchange(o->stored(value));
 }
 
 int frg_stage_times(float* ms, int n)
@@ -527,27 +498,9 @@ int frg_stage_times(float* ms, int n)
 
 int frg_get_option(const char* name)
 {
-    if (name && strcmp(name, "exact_blend") == 0) return exact_blend();
-    if (name && strcmp(name, "profile") == 0) return g_profile.load();
-    if (name && strcmp(name, "profile_stage") == 0) return g_profile_stage.load();
-    if (name && strcmp(name, "global_bins") == 0) return g_global_bins.load();
-    if (name && strcmp(name, "tight_binning") == 0) return g_tight_binning.load();
-    if (name && strcmp(name, "bwd_batch") == 0) return g_bwd_batch.load();
-    if (name && strcmp(name, "bwd_seg_log") == 0) return g_bwd_seg_log.load();
-    if (name && strcmp(name, "bwd_waves") == 0) return frg::g_bwd_waves;
-    if (name && strcmp(name, "fwd_order") == 0) return frg::g_fwd_order;
-    if (name && strcmp(name, "sh_dir_in_backward") == 0) return g_sh_no_dir.load();
-    if (name && strcmp(name, "counter_mailbox") == 0) return g_use_mailbox.load();
-    if (name && strcmp(name, "sparse_sh") == 0) return g_sparse_sh.load();
-    if (name && strcmp(name, "fwd_prefetch") == 0) return frg::g_fwd_prefetch;
-    if (name && strcmp(name, "bwd_heavy_first") == 0) return g_bwd_heavy_first.load();
-    if (name && strcmp(name, "clear_image_state") == 0) return g_clear_image_state.load();
-    if (name && strcmp(name, "sort_heavy_on_caller") == 0) return frg::g_sort_heavy_on_caller;
-    if (name && strcmp(name, "async_sh") == 0) return g_async_sh.load();
-    if (name && strcmp(name, "fused_small") == 0) return g_fused_small.load();
-    if (name && strcmp(name, "fwd_unroll8") == 0) return g_fwd_unroll8.load();
-    if (name && strcmp(name, "combine_blocks") == 0) return frg::g_combine_blocks;
-    return fail(FRG_EINVAL, "unknown option '%s'", name ? name : "(null)");
+    const Option* o = find_option(name);
+    if (!o || o->experiment) return fail(FRG_EINVAL, "unknown option '%s'", name ? name : "(null)");
+    return o->value == &g_exact_blend ? exact_blend() : o->value->load();
 }
 
 size_t frg_geometry_bytes(int P) { return frg::GeomState::carve(nullptr, P).bytes; }
@@ -629,7 +582,14 @@ static int forward_impl(const frg_forward_args& a)
     md.fwd_only = a.forward_only;
     const int exact = md.exact;
     const int seg_forced = g_bwd_seg_log.load();      // (read once: the size asked of the callback and the carve must agree)
-    auto bin_bytes = [seg_forced](int R_, int longest) { return frg::BinningState::carve(nullptr, R_, longest, seg_forced).bytes; };
+    // the binning chunk of R_ instances whose longest tile list has `longest` entries, from the caller's callback
+    auto alloc_binning = [&a, seg_forced](int R_, int longest, frg::BinningState* b_) -> int {
+        char* bin_chunk = a.binning_alloc(a.user, frg::BinningState::carve(nullptr, R_, longest, seg_forced).bytes);
+        if (!bin_chunk) return fail(FRG_EALLOC, "binning allocation callback returned null");
+        *b_ = frg::BinningState::carve(bin_chunk, R_, longest, seg_forced);
+        return FRG_OK;
+    };
+    const auto launch_blend_fwd = exact ? frg::launch_blend_fwd_exact : frg::launch_blend_fwd_fast;
     if (P < 0 || width <= 0 || height <= 0) return fail(FRG_EINVAL, "bad sizes P=%d W=%d H=%d", P, width, height);
     if (!out_color) return fail(FRG_EINVAL, "out_color is null");
     if (P == 0) {  // rasterize_points.cu:68,81: zero image, background not applied
@@ -669,7 +629,7 @@ static int forward_impl(const frg_forward_args& a)
     char* geom_chunk = a.geometry_alloc(a.user, frg_geometry_bytes(P));
     char* img_chunk = a.image_alloc(a.user, frg_image_bytes(width, height));
     if (!geom_chunk || !img_chunk) return fail(FRG_EALLOC, "allocation callback returned null");
-    note_forward(geom_chunk, exact, md.fwd_only != 0);
+    g_fwd_notes.begin(geom_chunk, exact, md.fwd_only != 0);
     const frg::GeomState g = frg::GeomState::carve(geom_chunk, P);
     const frg::ImageState img = frg::ImageState::carve(img_chunk, width, height, g_global_bins.load() != 0);
     int* const radii = a.radii ? a.radii : g.internal_radii;   // rasterizer_impl.cu:228-231
@@ -708,25 +668,24 @@ static int forward_impl(const frg_forward_args& a)
         if (!defer_sh || sh_forked || (at < sh_mode && at < 3)) return FRG_OK;
         sh_forked = true;
         sh_join.armed = true;
-        FRG_HIP(hipEventRecord(g_sh_side.geo_done, stream));
-        FRG_HIP(hipStreamWaitEvent(g_sh_side.stream, g_sh_side.geo_done, 0));
+        FRG_HIP(g_sh_side.fork_from(stream));
         {
             StageScope sc_(ST_SH_COLOR, g_sh_side.stream);
             FRG_HIP(frg::launch_sh_color(P, vp, in, radii, g, g_sh_side.stream));
         }
-        FRG_HIP(hipEventRecord(g_sh_side.sh_done, g_sh_side.stream));
+        FRG_HIP(hipEventRecord(g_sh_side.join, g_sh_side.stream));
         if (debug) FRG_HIP(hipStreamSynchronize(g_sh_side.stream));
         return FRG_OK;
     };
     { StageScope sc_(ST_PREPROCESS, stream); FRG_STAGE(frg::launch_preprocess_fwd(P, vp, in, radii, g, img, prefiltered, defer_sh, stream), "preprocess"); }
-    { const int rc_ = fork_sh(1); if (rc_ < 0) return rc_; }
+    FRG_TRY(fork_sh(1));
     // blocking form: the scan workgroups post the counters into this thread's pinned mailbox (frg_common.h) and the
     // host polls it, instead of a copy kernel + stream synchronisation behind the scan
     frg::Mailbox* mail = (capacity == 0 && !debug && g_use_mailbox.load(std::memory_order_relaxed)) ? g_mail.get() : nullptr;
     uint32_t mail_seq = 0;
     if (mail) { if (++g_mail.seq == 0) g_mail.seq = 1; mail_seq = g_mail.seq; }
     { StageScope sc_(ST_SCAN, stream); FRG_STAGE(frg::launch_scan(P, vp, g, img, (uint32_t)capacity, stream, mail, mail_seq), "scan"); }
-    { const int rc_ = fork_sh(2); if (rc_ < 0) return rc_; }
+    FRG_TRY(fork_sh(2));
 
     int index_bits = 1;
     while (index_bits < 32 && (1u << index_bits) < (uint32_t)P) index_bits++;
@@ -738,19 +697,15 @@ static int forward_impl(const frg_forward_args& a)
         FRG_HIP(hipStreamWaitEvent(pend->copy_stream, pend->scanned, 0));
         FRG_HIP(hipMemcpyAsync(pend->host, img.counters, sizeof(frg::Counters), hipMemcpyDeviceToHost, pend->copy_stream));
         FRG_HIP(hipEventRecord(pend->ev, pend->copy_stream));
-        char* bin_chunk = a.binning_alloc(a.user, bin_bytes(capacity, FRG_SORT_LDS_CAP + 1));
-        if (!bin_chunk) return fail(FRG_EALLOC, "binning allocation callback returned null");
-        const frg::BinningState b = frg::BinningState::carve(bin_chunk, capacity, FRG_SORT_LDS_CAP + 1, seg_forced);
+        frg::BinningState b;
+        FRG_TRY(alloc_binning(capacity, FRG_SORT_LDS_CAP + 1, &b));
         FRG_STAGE(frg::launch_sort_plan(T, nullptr, img.counters->class_count, img.class_tiles, img.ranges, b.big_plan, (uint32_t)capacity, stream), "sort plan");
         { StageScope sc_(ST_SCATTER, stream); FRG_STAGE(frg::launch_scatter(P, vp, radii, g, img, b, stream, g_ablate.load()), "scatter"); }
-        { const int rc_ = fork_sh(3); if (rc_ < 0) return rc_; }
+        FRG_TRY(fork_sh(3));
         { StageScope sc_(ST_SORT, stream); FRG_STAGE(frg::launch_tile_sort(T, nullptr, g_pending.have_hint ? g_pending.last_class_count : nullptr, img.counters->class_count, img.class_tiles, img.ranges, b.pairs, b.pairs_tmp, b.big_hist, b.big_plan, (uint32_t)capacity, 0, index_bits, b.point_list, stream), "sort"); }
-        if (defer_sh) { FRG_HIP(hipStreamWaitEvent(stream, g_sh_side.sh_done, 0)); sh_join.armed = false; }
+        if (defer_sh) { FRG_HIP(hipStreamWaitEvent(stream, g_sh_side.join, 0)); sh_join.armed = false; }
         StageScope sc_(ST_BLEND_FWD, stream);
-        if (exact)
-            FRG_STAGE(frg::launch_blend_fwd_exact(vp, g, img, b, background, out_color, stream), "blend");
-        else
-            FRG_STAGE(frg::launch_blend_fwd_fast(vp, g, img, b, background, out_color, stream), "blend");
+        FRG_STAGE(launch_blend_fwd(vp, g, img, b, background, out_color, stream, false, false, false), "blend");
         return R;
     }
 
@@ -767,14 +722,12 @@ static int forward_impl(const frg_forward_args& a)
             if (r > 0x7fffffffu) return fail(FRG_EINVAL, "num_rendered overflows int32");
             if (r > 0) {
                 R = (int)r;
-                char* bin_chunk = a.binning_alloc(a.user, bin_bytes(R, FRG_SORT_LDS_CAP + 1));
-                if (!bin_chunk) return fail(FRG_EALLOC, "binning allocation callback returned null");
-                b = frg::BinningState::carve(bin_chunk, R, FRG_SORT_LDS_CAP + 1, seg_forced);
+                FRG_TRY(alloc_binning(R, FRG_SORT_LDS_CAP + 1, &b));
                 if (g_mail.long_lists)
                     FRG_STAGE(frg::launch_sort_plan(T, nullptr, img.counters->class_count, img.class_tiles, img.ranges, b.big_plan, (uint32_t)R, stream, 1), "sort plan");
                 { StageScope sc_(ST_SCATTER, stream); FRG_STAGE(frg::launch_scatter(P, vp, radii, g, img, b, stream, g_ablate.load(), mail, mail_seq), "scatter"); }
-                { const int rc_ = fork_sh(3); if (rc_ < 0) return rc_; }
-                note_heavy_post(geom_chunk, mail, mail_seq);
+                FRG_TRY(fork_sh(3));
+                g_fwd_notes.update(geom_chunk, [&](FwdNote& n) { n.mail = mail; n.seq = mail_seq; });
                 g_mail.last_P = P; g_mail.last_seq = mail_seq;
                 early = true;
             }
@@ -794,30 +747,25 @@ static int forward_impl(const frg_forward_args& a)
     if (c.num_rendered > 0x7fffffffu) return fail(FRG_EINVAL, "num_rendered overflows int32");
     R = (int)c.num_rendered;
     const int max_tile = (int)c.max_tile_count;
-    note_rendered(geom_chunk, R);
+    g_fwd_notes.update(geom_chunk, [&](FwdNote& n) { n.rendered = R; });      // (a deferred forward does not know)
 
-    if (!early) {
-        char* bin_chunk = a.binning_alloc(a.user, bin_bytes(R, max_tile));
-        if (!bin_chunk) return fail(FRG_EALLOC, "binning allocation callback returned null");
-        b = frg::BinningState::carve(bin_chunk, R, max_tile, seg_forced);
-    }
+    if (!early) FRG_TRY(alloc_binning(R, max_tile, &b));
     const bool forked_plan = early && g_mail.long_lists;
     if (mail) g_mail.long_lists = c.class_count[4] > 0;
 
     // small frames (at most 2^20 instances: C2 has 350 000 in 2 500 lists of 140): the lists of up to 512 entries are sorted by the
     // forward blend's own workgroups (blend_impl.h FUSED) -- one launch and the point_list round trip less in a step that is a
     // chain of short launches; the longest-first tile order (class lists) is what the fused form walks
-    const bool fused_small = g_fused_small.load() != 0 && R > 0 && R <= (1 << 20) && frg::g_fwd_order != 0 && !(g_probe.load() & 1);
+    const bool fused_small = g_fused_small.load() != 0 && R > 0 && R <= (1 << 20) && frg::g_fwd_order.load() != 0 && !(g_probe.load() & 1);
     const bool probe_fwd = (g_probe.load() & 1) && R > 0 && !exact && g_probe_side.ensure();
     if (R > 0) {
         FRG_STAGE(frg::launch_sort_plan(T, c.class_count, img.counters->class_count, img.class_tiles, img.ranges, b.big_plan, (uint32_t)R, stream, forked_plan ? 2 : 0), "sort plan");
         if (!early) {
             { StageScope sc_(ST_SCATTER, stream); FRG_STAGE(frg::launch_scatter(P, vp, radii, g, img, b, stream, g_ablate.load()), "scatter"); }
-            { const int rc_ = fork_sh(3); if (rc_ < 0) return rc_; }
+            FRG_TRY(fork_sh(3));
         }
         if (probe_fwd) {
-            FRG_HIP(hipEventRecord(g_probe_side.fork, stream));
-            FRG_HIP(hipStreamWaitEvent(g_probe_side.stream, g_probe_side.fork, 0));
+            FRG_HIP(g_probe_side.fork_from(stream));
             FRG_HIP(frg::launch_blend_fwd_fast(vp, g, img, b, background, out_color, g_probe_side.stream));
             FRG_HIP(hipEventRecord(g_probe_side.join, g_probe_side.stream));
         }
@@ -826,9 +774,9 @@ static int forward_impl(const frg_forward_args& a)
     } else {
         // point_offsets must still be defined for backward
         FRG_STAGE(frg::launch_scatter(P, vp, radii, g, img, b, stream), "scatter");
-        { const int rc_ = fork_sh(3); if (rc_ < 0) return rc_; }
+        FRG_TRY(fork_sh(3));
     }
-    if (defer_sh) { FRG_HIP(hipStreamWaitEvent(stream, g_sh_side.sh_done, 0)); sh_join.armed = false; }
+    if (defer_sh) { FRG_HIP(hipStreamWaitEvent(stream, g_sh_side.join, 0)); sh_join.armed = false; }
     {
         StageScope sc_(ST_BLEND_FWD, stream);
         // A frame that does not fill the GPU (fewer than 1280 instances per tile of the image on average) and whose longest list
@@ -843,10 +791,7 @@ static int forward_impl(const frg_forward_args& a)
             long_lists = g_fwd_unroll8.load() == 2 ||
                          ((double)max_tile >= 3.5 * (double)R / (double)(active ? active : 1u) && (double)R < 1280.0 * (double)T);
         }
-        if (exact)
-            FRG_STAGE(frg::launch_blend_fwd_exact(vp, g, img, b, background, out_color, stream, md.fwd_only != 0, fused_small, long_lists), "blend");
-        else
-            FRG_STAGE(frg::launch_blend_fwd_fast(vp, g, img, b, background, out_color, stream, md.fwd_only != 0, fused_small, long_lists), "blend");
+        FRG_STAGE(launch_blend_fwd(vp, g, img, b, background, out_color, stream, md.fwd_only != 0, fused_small, long_lists), "blend");
     }
     return R;
 }
@@ -960,8 +905,8 @@ static int backward_impl(const frg_backward_args& a)
     //   * R: a note that says the forward rendered MORE instances than this call's R (slots and item lists would overrun) is
     //     checked against the stamped count the same way before the call is refused.
     int exact = a.exact_blend == 0 ? -1 : FwdModes::pick(a.exact_blend, 1, 0);
-    const int noted_rendered = forward_rendered(geom_buffer);
-    if ((forward_was_forward_only(geom_buffer) != 0 || (noted_rendered >= 0 && R < noted_rendered)) && phase != 2) {
+    const std::optional<FwdNote> note = g_fwd_notes.find(geom_buffer);
+    if ((!note || note->fwd_only || (note->rendered >= 0 && R < note->rendered)) && phase != 2) {
         frg::Counters* host = pinned_counters();
         if (!host) return fail(FRG_EHIP, "hipHostMalloc failed");
         const frg::ImageState img0 = frg::ImageState::carve(image_buffer, width, height, false);
@@ -999,11 +944,17 @@ static int backward_impl(const frg_backward_args& a)
     out.dL_dshell_verts = a.dL_dshell_cell_verts;
     out.row_live = a.row_live;
     const int pbw_flags = phase == 1 ? FRG_PBW_SUMS_ONLY : phase == 2 ? FRG_PBW_FROM_SUMS : 0;
+    // the per-Gaussian backward: each call site states its flags, its form (heavy_only), its stream and, in phase 1, what it leaves
+    auto preprocess_bwd = [&](int flags, bool heavy_only, hipStream_t s, unsigned long long* masks = nullptr, float* dirs = nullptr,
+                              int range_first = 0, int range_count = 0) {
+        return frg::launch_preprocess_bwd(P, vp, in, radii, g, img, slots, out, g_ablate.load(), flags, heavy_only, s, sums, masks, dirs,
+                                          range_first, range_count);
+    };
     if (phase == 2) {     // the sums are in the workspace: one launch, no slot reduction, hence no 16-wave form either
         if (!phase1_matches(workspace, geom_buffer, image_buffer, P, R))
             return fail(FRG_EINVAL, "backward phase 2 without a matching phase 1 on this workspace (same P, R, geometry and image buffers)");
         StageScope sc_(ST_PREPROCESS_BWD, stream);
-        FRG_STAGE(frg::launch_preprocess_bwd(P, vp, in, radii, g, img, slots, out, g_ablate.load(), pbw_flags | FRG_PBW_NO_HEAVY_LAUNCH, false, stream, sums), "preprocess_bwd (phase 2)");
+        FRG_STAGE(preprocess_bwd(pbw_flags | FRG_PBW_NO_HEAVY_LAUNCH, false, stream), "preprocess_bwd (phase 2)");
         return FRG_OK;
     }
     if (phase == 1) note_phase1(workspace, geom_buffer, image_buffer, P, R);
@@ -1015,10 +966,9 @@ static int backward_impl(const frg_backward_args& a)
     }
     const bool probe_bwd = (g_probe.load() & 2) && g_probe_side.ensure();
     if (probe_bwd) {   // timing experiment: the per-Gaussian backward beside the blend (it reads the previous frame's slots)
-        FRG_HIP(hipEventRecord(g_probe_side.fork, stream));
-        FRG_HIP(hipStreamWaitEvent(g_probe_side.stream, g_probe_side.fork, 0));
-        FRG_HIP(frg::launch_preprocess_bwd(P, vp, in, radii, g, img, slots, out, g_ablate.load(), pbw_flags, false, g_probe_side.stream, sums));
-        FRG_HIP(frg::launch_preprocess_bwd(P, vp, in, radii, g, img, slots, out, g_ablate.load(), pbw_flags, true, g_probe_side.stream, sums));
+        FRG_HIP(g_probe_side.fork_from(stream));
+        FRG_HIP(preprocess_bwd(pbw_flags, false, g_probe_side.stream));
+        FRG_HIP(preprocess_bwd(pbw_flags, true, g_probe_side.stream));
         FRG_HIP(hipEventRecord(g_probe_side.join, g_probe_side.stream));
     }
     if (!ranged || a.range_first == 0) {
@@ -1031,8 +981,7 @@ static int backward_impl(const frg_backward_args& a)
     if (probe_bwd) { FRG_HIP(hipStreamWaitEvent(stream, g_probe_side.join, 0)); return FRG_OK; }
     if (ranged) {      // phase 1 in pieces: the plain kernel over this range, whatever its waves own (no 16-wave side launch)
         StageScope sc_(ST_PREPROCESS_BWD, stream);
-        FRG_STAGE(frg::launch_preprocess_bwd(P, vp, in, radii, g, img, slots, out, g_ablate.load(), pbw_flags | FRG_PBW_NO_HEAVY_LAUNCH, false, stream, sums,
-                                             live_masks, dir_terms, a.range_first, a.range_count), "preprocess_bwd (phase 1, range)");
+        FRG_STAGE(preprocess_bwd(pbw_flags | FRG_PBW_NO_HEAVY_LAUNCH, false, stream, live_masks, dir_terms, a.range_first, a.range_count), "preprocess_bwd (phase 1, range)");
         return FRG_OK;
     }
     {
@@ -1040,7 +989,7 @@ static int backward_impl(const frg_backward_args& a)
         // (usually its workgroups find an empty list and leave)
         StageScope sc_(ST_PREPROCESS_BWD, stream);
         // the forward's scatter posted how many waves of Gaussians need the 16-wave form (Mailbox::heavy): none, usually
-        const int heavy = g_assume_no_heavy.load(std::memory_order_relaxed) ? 0 : debug ? -1 : heavy_waves_posted(geom_buffer);
+        const int heavy = g_assume_no_heavy.load(std::memory_order_relaxed) ? 0 : debug || !note ? -1 : note->heavy_waves_posted();
         const bool skip_heavy = heavy == 0;
         const bool side = !skip_heavy && !debug && g_bwd_side.ensure();
         // Known to exist: the few 16-wave workgroups go on the CALLER's stream and start at once on an empty GPU, the
@@ -1050,10 +999,10 @@ static int backward_impl(const frg_backward_args& a)
         const bool heavy_first = side && heavy > 0 && g_bwd_heavy_first.load(std::memory_order_relaxed);
         hipStream_t hs = side ? g_bwd_side.stream : stream;
         hipStream_t s_heavy = heavy_first ? stream : hs, s_plain = heavy_first ? hs : stream;
-        if (side) { FRG_HIP(hipEventRecord(g_bwd_side.fork, stream)); FRG_HIP(hipStreamWaitEvent(hs, g_bwd_side.fork, 0)); }
+        if (side) FRG_HIP(g_bwd_side.fork_from(stream));
         if (!skip_heavy)
-            FRG_STAGE(frg::launch_preprocess_bwd(P, vp, in, radii, g, img, slots, out, g_ablate.load(), pbw_flags, true, s_heavy, sums, live_masks, dir_terms), "preprocess_bwd (long runs)");
-        FRG_STAGE(frg::launch_preprocess_bwd(P, vp, in, radii, g, img, slots, out, g_ablate.load(), pbw_flags | (skip_heavy ? FRG_PBW_NO_HEAVY_LAUNCH : 0), false, s_plain, sums, live_masks, dir_terms), "preprocess_bwd");
+            FRG_STAGE(preprocess_bwd(pbw_flags, true, s_heavy, live_masks, dir_terms), "preprocess_bwd (long runs)");
+        FRG_STAGE(preprocess_bwd(pbw_flags | (skip_heavy ? FRG_PBW_NO_HEAVY_LAUNCH : 0), false, s_plain, live_masks, dir_terms), "preprocess_bwd");
         if (side) { FRG_HIP(hipEventRecord(g_bwd_side.join, hs)); FRG_HIP(hipStreamWaitEvent(stream, g_bwd_side.join, 0)); }
     }
     return FRG_OK;

@@ -30,6 +30,7 @@
 // floating-point contraction mode for everything below)
 #pragma once
 #include "frg_common.h"
+#include "kernels.h"
 #include "sort_lds.h"
 #include <algorithm>
 
@@ -763,17 +764,17 @@ blend_bwd_kernel(int T, int gx, int gy, int W, int H, const uint2* __restrict__ 
 
 
 // ---- launchers (instantiated by blend_exact.hip / blend_fast.hip with their arithmetic) ----------------------------------
-extern int g_fwd_order;       // tuning (frg_set_option("fwd_order")): 1 = forward blend walks the tiles longest list first
 template <bool EXACT>
 static hipError_t launch_blend_fwd_t(const ViewParams& vp, const GeomState& g, const ImageState& img, const BinningState& b,
                                      const float* bg, float* out_color, bool prefetch, hipStream_t s, bool forward_only = false,
                                      bool fused_sort = false, bool long_lists = false)
 {
     const int T = vp.gx * vp.gy;
+    const bool order = g_fwd_order.load(std::memory_order_relaxed) != 0;
 #define FRG_FWD(PF, FS, UN)                                                                                                \
     hipLaunchKernelGGL((blend_fwd_kernel<EXACT, PF, FS, UN>), dim3(xcd_grid_blocks(T)), dim3(BLEND_THREADS), 0, s, T, vp.gx, vp.W, vp.H, \
                        img.ranges, b.point_list, g.xydr, g.conic_opacity, g.rgb_clamped, bg, img.final_T, img.n_contrib,   \
-                       out_color, img.tile_work, forward_only ? nullptr : b.ckpt, img.final_C, g_fwd_order ? img.class_tiles : nullptr,             \
+                       out_color, img.tile_work, forward_only ? nullptr : b.ckpt, img.final_C, order ? img.class_tiles : nullptr, \
                        img.counters->class_count, b.seg_log, img.bwd_cnt, img.bwd_last, img.bwd_cap_b, b.bwd_full,         \
                        (uint32_t)BinningState::full_cap(b.carved_R), img.cutoff, img.counters, b.pairs)
     // long_lists (the host's reading of the frame's counters): the work sits in a few long lists -> eight entries per trip
@@ -790,7 +791,6 @@ static hipError_t launch_blend_fwd_t(const ViewParams& vp, const GeomState& g, c
 // queue 0.55 / 0.39, 8192 0.41 / 0.39; segments of 512 (13 000 items at C3) -- 8192 waves 0.386 / 0.370, 16384 0.363 / 0.368,
 // 32768 0.366 / 0.371: one item per wave and the hardware's dispatcher, while the items fit the grid
 #define FRG_BWD_MAX_WAVES 16384
-extern int g_bwd_waves;       // tuning (frg_set_option("bwd_waves")): single-wave workgroups of the backward blend (0: the default)
 template <bool EXACT>
 static hipError_t launch_blend_bwd_t(const ViewParams& vp, const GeomState& g, const ImageState& img, const BinningState& b,
                                      const float* bg, const float* dL_dpix, float* slots, uint32_t R, int batch, hipStream_t s, bool as_stamped)
@@ -799,7 +799,8 @@ static hipError_t launch_blend_bwd_t(const ViewParams& vp, const GeomState& g, c
     // waves: one per item while the frame has at most FRG_BWD_MAX_WAVES items (an upper bound on their number), beyond
     // that the waves stride
     const int bound = (int)std::min<size_t>((size_t)T + BinningState::full_cap(R), (size_t)FRG_BWD_MAX_WAVES);
-    const int nwaves = ((g_bwd_waves > 0 ? g_bwd_waves : bound) + 7) / 8 * 8;
+    const int waves_asked = g_bwd_waves.load(std::memory_order_relaxed);
+    const int nwaves = ((waves_asked > 0 ? waves_asked : bound) + 7) / 8 * 8;
 #define FRG_BWD(B)                                                                                                         \
     hipLaunchKernelGGL((blend_bwd_kernel<EXACT, B>), dim3(nwaves), dim3(64), 0, s, T, vp.gx, vp.gy, vp.W, vp.H,               \
                        img.ranges, b.point_list, g.xydr, g.conic_opacity, g.rgb_clamped, g.point_offsets, bg, img.final_T,     \

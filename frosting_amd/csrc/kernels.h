@@ -4,7 +4,59 @@
 #include "frg_common.h"
 #include "raw_params.h"
 
+#include <atomic>
+
 namespace frg {
+
+// Process-wide options that a launcher reads (frg_set_option; defined with the option table in api.hip).  Set by one host
+// thread, read by another (autograd runs the backward on its engine thread): atomics, relaxed loads on the launch paths.
+extern std::atomic<int> g_rows_grid;              // "rows_grid": workgroups of the row-ordered scatter (0: by the model's size; > 0: timing experiments)
+extern std::atomic<int> g_sort_heavy_on_caller;   // "sort_heavy_on_caller": the long lists' chain of kernels on the caller's stream when they are known to exist
+extern std::atomic<int> g_fwd_prefetch;           // "fwd_prefetch": the forward blend requests round r + 1's records before it processes round r
+extern std::atomic<int> g_fwd_order;              // "fwd_order": 1 = the forward blend takes the tiles longest list first, 0 = XCD band by band (rounds 1-3)
+extern std::atomic<int> g_bwd_waves;              // "bwd_waves": single-wave workgroups of the backward blend (0: the default, 16 per CU)
+extern std::atomic<int> g_combine_blocks;         // "combine_blocks": blocks of 64 Gaussians per combine tile (0: by the number of views)
+
+// A non-blocking stream beside the caller's, with the two events that order it against the caller's stream.  Kept one per
+// host thread (thread_local at its user) and re-made when that thread's current device changes.
+struct SideStream {
+    enum Priority { LOWEST, DEFAULT, HIGHEST };
+    Priority priority = DEFAULT;
+    hipStream_t stream = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;   // recorded on the caller's stream, the side waits | recorded on the side, the caller waits
+    int device = -1;
+    bool ensure()
+    {
+        int dev = -1;
+        return hipGetDevice(&dev) == hipSuccess && ensure_on(dev);
+    }
+    bool ensure_on(int dev)
+    {
+        if (dev == device) return true;
+        // first use on this thread, or the caller switched devices: (re)create on the current one
+        if (stream) (void)hipStreamDestroy(stream);
+        if (fork) (void)hipEventDestroy(fork);
+        if (join) (void)hipEventDestroy(join);
+        stream = nullptr; fork = nullptr; join = nullptr; device = -1;
+        if (priority == DEFAULT) {
+            if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return false;
+        } else {
+            int least = 0, greatest = 0;
+            (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+            if (hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, priority == LOWEST ? least : greatest) != hipSuccess) return false;
+        }
+        if (hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess) return false;
+        if (hipEventCreateWithFlags(&join, hipEventDisableTiming) != hipSuccess) return false;
+        device = dev;
+        return true;
+    }
+    // the side stream waits for what the caller's stream holds so far
+    hipError_t fork_from(hipStream_t caller)
+    {
+        const hipError_t e = hipEventRecord(fork, caller);
+        return e != hipSuccess ? e : hipStreamWaitEvent(stream, fork, 0);
+    }
+};
 
 struct FwdInputs {
     const float *means3D, *scales, *rotations, *opacities, *shs, *cov3D_precomp, *colors_precomp;
@@ -22,7 +74,6 @@ hipError_t launch_scan(int P, const ViewParams& vp, const GeomState& g, const Im
                        Mailbox* mail = nullptr, uint32_t seq = 0);
 hipError_t launch_scatter(int P, const ViewParams& vp, const int* radii, const GeomState& g, const ImageState& img,
                           const BinningState& b, hipStream_t s, int ablate = 0, Mailbox* mail = nullptr, uint32_t seq = 0);
-extern int g_rows_grid;   // workgroups of the row-ordered scatter (tuning)
 hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmatrix, unsigned char* present, hipStream_t s);
 
 // class_count: host copy of the per-class tile counts, or nullptr when they are only known on the
@@ -32,10 +83,6 @@ hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmat
 // count the binning chunk was carved with); max_tile_count: longest list (0: unknown, kernels stride); index_bits:
 // bits needed for a Gaussian index (tie order = ascending index)
 // to be called before launch_scatter (same arguments as launch_tile_sort's): plans the sort of the long lists
-extern int g_sort_heavy_on_caller;
-extern int g_fwd_prefetch;
-extern int g_fwd_order;
-extern int g_bwd_waves;         // tuning: single-wave workgroups of the backward blend (0: the default, 16 per CU)
 hipError_t launch_sort_plan(int T, const uint32_t* class_count, const uint32_t* class_count_dev, const uint32_t* class_tiles,
                             const uint2* ranges, uint32_t* big_plan, uint32_t R, hipStream_t stream, int fork_mode = 0);
 hipError_t launch_tile_sort(int T, const uint32_t* class_count, const uint32_t* grid_hint, const uint32_t* class_count_dev,
@@ -106,7 +153,6 @@ hipError_t launch_pack_sum_rows(int first, int n, uint32_t capacity, const unsig
 // in: means3D, shs, scales, rotations, opacities (or their raw forms); out: dL_dmean3D, dL_dscale, dL_drot, dL_dopacity, dL_dsh
 // workspace: combine_workspace_bytes(n_views, capacity) (256 bytes since the pass became one kernel that stages nothing in HBM);
 size_t combine_workspace_bytes(int n_views, size_t capacity);
-extern int g_combine_blocks;   // tuning: blocks of 64 Gaussians per combine tile (0: by the number of views)
 hipError_t launch_backward_combine(int first, int n, int n_views, const void* packets, size_t packet_stride_bytes, uint32_t capacity,
                                    const FwdInputs& in, const BwdOutputs& out, unsigned long long* status, uint32_t seq, unsigned char* row_live,
                                    char* workspace, hipStream_t s);

@@ -1108,7 +1108,6 @@ mark_visible_kernel(int P, const float* __restrict__ means3D, const float* __res
 
 // ---- host launchers -----------------------------------------------------------
 // workgroups of the cell-ordered scatter (tuning knob: frg_set_option("rows_grid")), 2 per CU by default
-int g_rows_grid = 0;     // 0: by the model's size (launch_scatter); > 0: timing experiments
 
 // The scatter runs over cell-ordered records (reorder_kernel + scatter_rows_kernel) in the reference-identical
 // binning mode; tight binning keeps the scatter in the caller's order (it would evaluate the per-instance tile test in
@@ -1229,7 +1228,8 @@ hipError_t launch_scatter(int P, const ViewParams& vp, const int* radii, const G
         // ... and more than two per CU for the large ones (r05, shares dealt evenly to the XCDs whatever the grid; same box, scatter
         // stage at C3 / C4): 512 workgroups 0.088 / 0.098 ms, 640 0.081 / 0.098, 768 0.080 / 0.089, 1024 0.081 / 0.089, 1536 0.078 / 0.089
         const int by_size = std::min(1024, std::max(64, P / 768));
-        const int grid = ((std::max(need, g_rows_grid > 0 ? g_rows_grid : by_size) + FRG_NUM_XCD - 1) / FRG_NUM_XCD) * FRG_NUM_XCD;
+        const int rows_asked = g_rows_grid.load(std::memory_order_relaxed);
+        const int grid = ((std::max(need, rows_asked > 0 ? rows_asked : by_size) + FRG_NUM_XCD - 1) / FRG_NUM_XCD) * FRG_NUM_XCD;
         hipError_t e = allow_big_lds(scatter_rows_kernel, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid), dim3(FRG_BIN_THREADS), lds, s, T, vp.gx, vp.gy, g.row_records,

@@ -565,7 +565,6 @@ size_t combine_workspace_bytes(int n_views, size_t capacity)
     return 256;                 // the pass stages nothing in HBM any more; the argument stays in the ABI
 }
 
-int g_combine_blocks = 0;       // tuning (frg_set_option("combine_blocks")): blocks of 64 Gaussians per tile, 0 = by the number of views
 
 template <bool RAW>
 static void launch_tile(int B, int nblk, hipStream_t s, int first, int n, int n_views, const uint32_t* pk, size_t stride_w, uint32_t capacity,
@@ -587,7 +586,8 @@ hipError_t launch_backward_combine(int first, int n, int n_views, const void* pa
     const size_t stride_w = packet_stride_bytes / 4;
     const int nblk = (int)sum_packet_blocks((size_t)n);
     // a tile of a few hundred pairs where one Gaussian in eight has a row per view (C3); any density is handled (more passes)
-    const int B = g_combine_blocks > 0 ? g_combine_blocks : n_views >= 6 ? 3 : n_views >= 3 ? 6 : n_views == 2 ? 12 : 24;
+    const int asked = g_combine_blocks.load(std::memory_order_relaxed);
+    const int B = asked > 0 ? asked : n_views >= 6 ? 3 : n_views >= 3 ? 6 : n_views == 2 ? 12 : 24;
     const bool raw = in.raw.raw_opacity || in.raw.raw_scale || in.raw.raw_rot;
     if (raw) launch_tile<true>(B, nblk, s, first, n, n_views, pk, stride_w, capacity, in, out, row_live, status, seq);
     else launch_tile<false>(B, nblk, s, first, n, n_views, pk, stride_w, capacity, in, out, row_live, status, seq);

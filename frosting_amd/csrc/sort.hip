@@ -417,8 +417,8 @@ static hipError_t launch_lds_class(int count, const uint32_t* tile_list, const u
 // exactly the tiles of its class (lists built by scan_kernel): a grid of all T tiles with
 // early exits was dominated by dispatching ~6000 no-op 1024-thread workgroups.
 struct SortStreams {
-    hipStream_t side[2] = {nullptr, nullptr};
-    hipEvent_t fork = nullptr, join[2] = {nullptr, nullptr}, plan_fork = nullptr, plan_done = nullptr;
+    SideStream side[2];          // side[0].fork: the sort's fork; side[1].fork: the plan's (launch_sort_plan)
+    hipEvent_t plan_done = nullptr;
     bool plan_on_side = false;   // the last big_plan_kernel went to side[1] (plan_done says when it is through)
     int device = -1;
     bool ensure()
@@ -426,23 +426,9 @@ struct SortStreams {
         int dev = -1;
         if (hipGetDevice(&dev) != hipSuccess) return false;
         if (dev == device) return true;
-        // first use on this thread, or the caller switched devices: (re)create on the current one
-        for (int i = 0; i < 2; i++) {
-            if (side[i]) (void)hipStreamDestroy(side[i]);
-            if (join[i]) (void)hipEventDestroy(join[i]);
-            side[i] = nullptr; join[i] = nullptr;
-        }
-        if (fork) (void)hipEventDestroy(fork);
-        if (plan_fork) (void)hipEventDestroy(plan_fork);
         if (plan_done) (void)hipEventDestroy(plan_done);
-        fork = nullptr; plan_fork = nullptr; plan_done = nullptr;
-        device = -1;
-        for (int i = 0; i < 2; i++) {
-            if (hipStreamCreateWithFlags(&side[i], hipStreamNonBlocking) != hipSuccess) return false;
-            if (hipEventCreateWithFlags(&join[i], hipEventDisableTiming) != hipSuccess) return false;
-        }
-        if (hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess) return false;
-        if (hipEventCreateWithFlags(&plan_fork, hipEventDisableTiming) != hipSuccess) return false;
+        plan_done = nullptr; device = -1;
+        if (!side[0].ensure_on(dev) || !side[1].ensure_on(dev)) return false;
         if (hipEventCreateWithFlags(&plan_done, hipEventDisableTiming) != hipSuccess) return false;
         device = dev;
         return true;
@@ -466,7 +452,6 @@ static hipError_t allow_sort_lds(K kernel, size_t lds)
 }
 
 static thread_local SortStreams g_sort_streams;
-int g_sort_heavy_on_caller = 1;   // frg_set_option("sort_heavy_on_caller")
 
 // The long lists' plan only needs the scan's outputs (ranges, the class lists): launched on the sort's second side
 // stream BEFORE the scatter is enqueued, its single workgroup's latency chain hides under the scatter.
@@ -480,10 +465,10 @@ hipError_t launch_sort_plan(int T, const uint32_t* class_count, const uint32_t* 
     hipStream_t s2 = stream;
     hipError_t e;
     if (ss.ensure()) {
-        if (fork_mode != 2 && (e = hipEventRecord(ss.plan_fork, stream)) != hipSuccess) return e;
+        if (fork_mode != 2 && (e = hipEventRecord(ss.side[1].fork, stream)) != hipSuccess) return e;
         if (fork_mode == 1) return hipSuccess;
-        if ((e = hipStreamWaitEvent(ss.side[1], ss.plan_fork, 0)) != hipSuccess) return e;
-        s2 = ss.side[1];
+        if ((e = hipStreamWaitEvent(ss.side[1].stream, ss.side[1].fork, 0)) != hipSuccess) return e;
+        s2 = ss.side[1].stream;
     } else if (fork_mode == 1) return hipSuccess;
     hipLaunchKernelGGL(big_plan_kernel, dim3(1), dim3(1024), 0, s2, class_tiles + (size_t)4 * T, class_count_dev + 4, ranges, big_plan, R);
     ss.plan_on_side = s2 != stream;
@@ -524,8 +509,8 @@ hipError_t launch_tile_sort(int T, const uint32_t* class_count, const uint32_t* 
     // 0.209 ms, in-process A/B): the small classes then start late on a side stream instead of at once.
     hipStream_t lane[3] = {stream, stream, stream};
     int on[4] = {2, 2, 1, 0};                    // lane of: chain, (4096,8192], (2048,4096], small classes
-    if (forked) { lane[1] = ss.side[0]; lane[2] = ss.side[1]; }
-    if (forked && class_count && c4 > 0 && g_sort_heavy_on_caller) {
+    if (forked) { lane[1] = ss.side[0].stream; lane[2] = ss.side[1].stream; }
+    if (forked && class_count && c4 > 0 && g_sort_heavy_on_caller.load(std::memory_order_relaxed)) {
         const double w[4] = {c4 ? 1e30 : 0.0, c3 * 8192.0, c2 * 4096.0, c1 * 2048.0 + c0 * 512.0};
         int order[4] = {0, 1, 2, 3};
         for (int i = 1; i < 4; i++)
@@ -544,13 +529,13 @@ hipError_t launch_tile_sort(int T, const uint32_t* class_count, const uint32_t* 
     for (int g = 0; g < 4; g++) if (has[g]) use_lane[on[g]] = true;
     const bool use_s1 = forked && use_lane[1], use_s2 = forked && use_lane[2];
     if (forked) {
-        if ((e = hipEventRecord(ss.fork, stream)) != hipSuccess) return e;
-        if (use_s1 && (e = hipStreamWaitEvent(lane[1], ss.fork, 0)) != hipSuccess) return e;
-        if (use_s2 && (e = hipStreamWaitEvent(lane[2], ss.fork, 0)) != hipSuccess) return e;
+        if ((e = hipEventRecord(ss.side[0].fork, stream)) != hipSuccess) return e;
+        if (use_s1 && (e = hipStreamWaitEvent(lane[1], ss.side[0].fork, 0)) != hipSuccess) return e;
+        if (use_s2 && (e = hipStreamWaitEvent(lane[2], ss.side[0].fork, 0)) != hipSuccess) return e;
     }
     const hipStream_t s4 = lane[on[0]], s3 = lane[on[1]], s2c = lane[on[2]], s10 = lane[on[3]];
     // the chain follows its plan (launch_sort_plan: on the second side stream, forked before the scatter)
-    if (c4 && ss.plan_on_side && s4 != ss.side[1] && (e = hipStreamWaitEvent(s4, ss.plan_done, 0)) != hipSuccess) return e;
+    if (c4 && ss.plan_on_side && s4 != ss.side[1].stream && (e = hipStreamWaitEvent(s4, ss.plan_done, 0)) != hipSuccess) return e;
     const hipStream_t s2 = s4;     // (name used by the chain's launches below)
     // size classes: (0,512] 1 wave, (512,2048] 4 waves, (2048,4096] 8 waves, (4096,8192] 8 waves x 16 elements,
     // >8192 sorted chunks + splitters (beyond FRG_SORT_MID_MAX: global LSD passes); longest-running classes first
@@ -606,12 +591,12 @@ hipError_t launch_tile_sort(int T, const uint32_t* class_count, const uint32_t* 
     if ((e = launch_lds_class<1, 512>(c0, class_tiles, len, ranges, pairs, point_list, s10)) != hipSuccess) return e;
     if (forked) {
         if (use_s1) {
-            if ((e = hipEventRecord(ss.join[0], lane[1])) != hipSuccess) return e;
-            if ((e = hipStreamWaitEvent(stream, ss.join[0], 0)) != hipSuccess) return e;
+            if ((e = hipEventRecord(ss.side[0].join, lane[1])) != hipSuccess) return e;
+            if ((e = hipStreamWaitEvent(stream, ss.side[0].join, 0)) != hipSuccess) return e;
         }
         if (use_s2) {
-            if ((e = hipEventRecord(ss.join[1], lane[2])) != hipSuccess) return e;
-            if ((e = hipStreamWaitEvent(stream, ss.join[1], 0)) != hipSuccess) return e;
+            if ((e = hipEventRecord(ss.side[1].join, lane[2])) != hipSuccess) return e;
+            if ((e = hipStreamWaitEvent(stream, ss.side[1].join, 0)) != hipSuccess) return e;
         }
     }
     return hipSuccess;

@@ -50,6 +50,94 @@ def test_state_size_queries_and_options():
             assert _lib.set_option(knob, 1) < 0 and "FROSTING_EXPERIMENTS" in _lib.last_error()
 
 
+# Requests put to every option, and what frg_set_option stores for each (read off csrc/api.hip as it stood before the
+# option table: literals, not computed by the library under test).
+_REQUESTS = (-1, 0, 1, 2, 3, 4, 7, 8, 9, 10, 11, 100)
+_FLAG = (1, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1)                    # v ? 1 : 0
+_NOT_NEGATIVE = (0, 0, 1, 2, 3, 4, 7, 8, 9, 10, 11, 100)        # v < 0 ? 0 : v
+_OPTIONS = {                                                     # name: (default, stored value per request)
+    "exact_blend": (0, _FLAG), "profile": (0, _FLAG), "global_bins": (0, _FLAG), "tight_binning": (0, _FLAG),
+    "clear_image_state": (0, _FLAG), "sh_dir_in_backward": (0, _FLAG),
+    "counter_mailbox": (1, _FLAG), "sparse_sh": (1, _FLAG), "fwd_prefetch": (1, _FLAG), "bwd_heavy_first": (1, _FLAG),
+    "fwd_order": (1, _FLAG), "sort_heavy_on_caller": (1, _FLAG), "fused_small": (1, _FLAG),
+    "profile_stage": (-1, (-1, 0, 1, 2, 3, 4, 7, -1, -1, -1, -1, -1)),      # eight stages
+    "bwd_batch": (3, (3, 3, 3, 2, 3, 3, 3, 3, 3, 3, 3, 3)),
+    "bwd_seg_log": (0, (0, 0, 0, 0, 0, 0, 0, 8, 9, 10, 0, 0)),
+    "bwd_waves": (0, _NOT_NEGATIVE), "combine_blocks": (0, _NOT_NEGATIVE),
+    "async_sh": (0, (1, 0, 1, 2, 3, 1, 1, 1, 1, 1, 1, 1)),
+    "fwd_unroll8": (1, (1, 0, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1)),
+}
+_EXPERIMENT_KNOBS = {                                            # set only, and only under FROSTING_EXPERIMENTS=1
+    "ablate": (0, _REQUESTS), "probe": (0, _REQUESTS), "assume_no_heavy": (0, _FLAG),
+    "rows_grid": (0, (0, 0, 8, 8, 8, 8, 8, 8, 9, 10, 11, 100)),
+}
+_OPTION_CHILD = r"""
+import ctypes, json, os, sys
+path, requests, options, knobs = json.loads(sys.argv[1])
+L = ctypes.CDLL(path)
+L.frg_last_error.restype = ctypes.c_char_p
+L.frg_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int]
+L.frg_get_option.argtypes = [ctypes.c_char_p]
+err = lambda: L.frg_last_error().decode()
+# a fresh process: every option answers get with its default
+for name, (default, _) in options.items():
+    assert L.frg_get_option(name.encode()) == default, (name, "default", L.frg_get_option(name.encode()), default)
+for name, (default, stored) in options.items():
+    previous = default
+    for v, expect in zip(requests, stored):
+        got = L.frg_set_option(name.encode(), v)
+        assert got == previous, (name, v, "set returned", got, "previous", previous)
+        assert L.frg_get_option(name.encode()) == expect, (name, v, "get", L.frg_get_option(name.encode()), "expected", expect)
+        previous = expect
+    assert L.frg_set_option(name.encode(), default) == previous and L.frg_get_option(name.encode()) == default, name
+# unknown names, NULL included, from both
+for fn in (lambda n: L.frg_set_option(n, 1), L.frg_get_option):
+    assert fn(b"no_such_option") == -1 and err() == "unknown option 'no_such_option'", err()
+    assert fn(None) == -1 and err() == "unknown option '(null)'", err()
+experiments = os.environ.get("FROSTING_EXPERIMENTS") == "1"
+for name, (default, stored) in knobs.items():
+    assert L.frg_get_option(name.encode()) == -1 and err() == "unknown option '%s'" % name, (name, err())
+    if not experiments:
+        for v in requests:
+            assert L.frg_set_option(name.encode(), v) == -1, (name, v)
+            assert err() == ("option '%s' is a timing experiment (results are wrong by design): start the process with "
+                             "FROSTING_EXPERIMENTS=1 to use it" % name), err()
+        continue
+    previous = default
+    for v, expect in zip(requests, stored):     # (no get: the stored value is what the next set returns)
+        got = L.frg_set_option(name.encode(), v)
+        assert got == previous, (name, v, "set returned", got, "previous", previous)
+        previous = expect
+    assert L.frg_set_option(name.encode(), default) == previous and L.frg_set_option(name.encode(), default) == default, name
+for name, (default, _) in options.items():
+    assert L.frg_get_option(name.encode()) == default, (name, "left at", L.frg_get_option(name.encode()))
+print("options ok")
+"""
+
+
+def _run_option_child(options, knobs, **env_changes):
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("FROSTING_EXPERIMENTS", "FROSTING_EXACT_BLEND")}
+    env.update(env_changes)
+    r = subprocess.run([sys.executable, "-c", _OPTION_CHILD, json.dumps([_lib.LIB_PATH, _REQUESTS, options, knobs])],
+                       env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "options ok", r.stdout + r.stderr
+
+
+def test_option_table_defaults_and_normalisation():
+    """Every option of frg_set_option / frg_get_option, in a fresh process (ctypes only, no GPU): get returns the default;
+    for each request of _REQUESTS set returns the previously stored value and get the value the option's rule prescribes;
+    the defaults are put back.  The four timing-experiment knobs answer set only in a process started with
+    FROSTING_EXPERIMENTS=1 (the gate is read once per process) and never answer get."""
+    assert len(_OPTIONS) == 20 and len(_EXPERIMENT_KNOBS) == 4
+    _run_option_child(_OPTIONS, _EXPERIMENT_KNOBS)                                   # knobs refused
+    _run_option_child(_OPTIONS, _EXPERIMENT_KNOBS, FROSTING_EXPERIMENTS="1")         # knobs set
+    # exact_blend's default is the environment's, resolved when first asked for: here by the first set, which returns it
+    _run_option_child({"exact_blend": (1, _FLAG)}, {}, FROSTING_EXACT_BLEND="1")
+
+
 def test_settings_fields_match_reference_order():
     assert GaussianRasterizationSettings._fields == (
         "image_height", "image_width", "tanfovx", "tanfovy", "bg", "scale_modifier", "viewmatrix", "projmatrix",
