@@ -120,6 +120,13 @@ class CombineArgs(C.Structure):
                 ("hip_stream", C.c_void_p)]
 
 
+class DensifyParams(C.Structure):
+    """frg_densify_params (include/frosting_rasterizer.h)."""
+    _fields_ = [("struct_size", C.c_size_t),
+                ("max_grad", C.c_double), ("min_opacity", C.c_double), ("extent", C.c_double), ("percent_dense", C.c_double),
+                ("prune_big_points", C.c_int)]
+
+
 # The parameters of the reference-shaped entry points are fields of the structs: their positional order, written once.
 # (argtypes of the functions and the arguments of a call are both derived from it.)
 FORWARD_POSITIONAL = [name for name, _ in ForwardArgs._fields_[1:ForwardArgs._fields_.index(("hip_stream", C.c_void_p)) + 1]]
@@ -320,6 +327,18 @@ def lib():
     L.frg_combine_workspace_bytes.argtypes = [i, C.c_longlong]
     L.frg_backward_combine.restype = i
     L.frg_backward_combine.argtypes = [C.POINTER(CombineArgs)]
+    if hasattr(L, "frg_densify_plan"):            # (absent from an older library loaded through FROSTING_LIB for an A/B)
+        L.frg_densify_accumulate.restype = i
+        L.frg_densify_accumulate.argtypes = [i, vp, vp, vp, vp, vp, vp, vp]
+        L.frg_densify_workspace_bytes.restype = sz
+        L.frg_densify_workspace_bytes.argtypes = [i]
+        L.frg_densify_plan.restype = i
+        L.frg_densify_plan.argtypes = [i, vp, vp, vp, vp, C.POINTER(DensifyParams), vp, vp, vp, sz, vp]
+        L.frg_densify_apply.restype = i
+        L.frg_densify_apply.argtypes = [i, i, vp, i, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                        C.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.frg_reset_opacity.restype = i
+        L.frg_reset_opacity.argtypes = [i, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -372,4 +391,5 @@ EXPORTED_SYMBOLS = [
     "frg_forward_deferred", "frg_forward_finish", "frg_forward_ex", "frg_backward_ex", "frg_adam_step",
     "frg_photometric_workspace_bytes", "frg_photometric_loss", "frg_activate", "frg_activate_backward",
     "frg_knn_workspace_bytes", "frg_knn_mean_dist2", "frg_shell_points", "frg_shell_points_backward",
+    "frg_densify_accumulate", "frg_densify_workspace_bytes", "frg_densify_plan", "frg_densify_apply", "frg_reset_opacity",
 ]

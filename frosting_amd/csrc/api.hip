@@ -1339,4 +1339,83 @@ int frg_shell_points_backward(int P, const float* bary_logits, const float* cell
     return FRG_OK;
 }
 
+// ---- adaptive density control (densify.hip) ----
+int frg_densify_accumulate(int P, const int* radii, const float* dL_dmean2D, const unsigned char* row_live,
+                           float* xyz_gradient_accum, float* denom, float* max_radii2D, void* hip_stream)
+{
+    if (P < 0) return fail(FRG_EINVAL, "P < 0");
+    if (P == 0) return FRG_OK;
+    if (!radii || !dL_dmean2D || !xyz_gradient_accum || !denom || !max_radii2D) return fail(FRG_EINVAL, "null pointer");
+    FRG_HIP(frg::launch_densify_accumulate(P, radii, dL_dmean2D, row_live, xyz_gradient_accum, denom, max_radii2D,
+                                           (hipStream_t)hip_stream));
+    return FRG_OK;
+}
+
+size_t frg_densify_workspace_bytes(int P) { return P > 0 ? frg::densify_workspace_bytes(P) : 0; }
+
+int frg_densify_plan(int P, const float* raw_scales, const float* raw_opacities, const float* xyz_gradient_accum,
+                     const float* denom, const frg_densify_params* params, int* plan, int* record,
+                     char* workspace, size_t workspace_bytes, void* hip_stream)
+{
+    if (P <= 0) return fail(FRG_EINVAL, "P = %d: a model to densify has Gaussians", P);
+    if (P > 0x7fffffff / 3) return fail(FRG_EINVAL, "P = %d: up to 3 P resulting rows must fit 31 bits", P);
+    if (!params || params->struct_size < sizeof(frg_densify_params)) return fail(FRG_EINVAL, "frg_densify_params: struct_size");
+    if (!raw_scales || !raw_opacities || !xyz_gradient_accum || !denom || !plan || !record) return fail(FRG_EINVAL, "null pointer");
+    if (!workspace || workspace_bytes < frg_densify_workspace_bytes(P))
+        return fail(FRG_EALLOC, "workspace too small: need %zu bytes", frg_densify_workspace_bytes(P));
+    if (reinterpret_cast<uintptr_t>(workspace) % 4 != 0) return fail(FRG_EINVAL, "workspace must be 4-byte aligned");
+    // the reference compares float32 tensors with Python floats: the products are formed in double and rounded once
+    frg::DensifyThresholds t;
+    t.max_grad = (float)params->max_grad;
+    t.min_opacity = (float)params->min_opacity;
+    t.dense_scale = (float)(params->percent_dense * params->extent);
+    t.world_scale = (float)(0.1 * params->extent);
+    t.prune_world = params->prune_big_points ? 1 : 0;
+    FRG_HIP(frg::launch_densify_plan(P, raw_scales, raw_opacities, xyz_gradient_accum, denom, t, plan, record, workspace,
+                                     (hipStream_t)hip_stream));
+    return FRG_OK;
+}
+
+int frg_densify_apply(int P, int P_out, const int* plan, int n_groups, const int* group_width,
+                      const long long* src_offsets, const long long* dst_offsets, long long out_numel, const float* noise,
+                      const float* params, const float* exp_avg, const float* exp_avg_sq,
+                      float* out_params, float* out_exp_avg, float* out_exp_avg_sq, void* hip_stream)
+{
+    if (P <= 0 || P_out < 0) return fail(FRG_EINVAL, "P = %d, P_out = %d", P, P_out);
+    if (n_groups < 3 || n_groups > FRG_DENSIFY_MAX_GROUPS) return fail(FRG_EINVAL, "n_groups = %d: 3 .. %d", n_groups, FRG_DENSIFY_MAX_GROUPS);
+    if (!plan || !group_width || !src_offsets || !dst_offsets || !params || !exp_avg || !exp_avg_sq) return fail(FRG_EINVAL, "null pointer");
+    if (P_out > 0 && (!out_params || !out_exp_avg || !out_exp_avg_sq)) return fail(FRG_EINVAL, "null output buffer");
+    if (group_width[0] != 3 || group_width[1] != 3 || group_width[2] != 4)
+        return fail(FRG_EINVAL, "the first three groups must be means3D [P,3], scales [P,3], rotations [P,4]");
+    frg::DensifyGroups g{};
+    g.count = n_groups;
+    g.dst_total = out_numel;
+    for (int k = 0; k < n_groups; k++) {
+        if (group_width[k] <= 0 || src_offsets[k] < 0 || dst_offsets[k] < 0 || (src_offsets[k] & 3) || (dst_offsets[k] & 3))
+            return fail(FRG_EINVAL, "group %d: width %d, offsets %lld -> %lld (offsets are multiples of 4 elements)", k, group_width[k],
+                        src_offsets[k], dst_offsets[k]);
+        const long long end = k + 1 < n_groups ? dst_offsets[k + 1] : out_numel;
+        if (dst_offsets[k] + (long long)P_out * group_width[k] > end || end - (dst_offsets[k] + (long long)P_out * group_width[k]) > 64)
+            return fail(FRG_EINVAL, "group %d: %d rows of %d elements from %lld do not end at %lld", k, P_out, group_width[k], dst_offsets[k], end);
+        if (k + 1 < n_groups && src_offsets[k] + (long long)P * group_width[k] > src_offsets[k + 1])
+            return fail(FRG_EINVAL, "group %d overlaps the next in the old layout", k);
+        g.width[k] = group_width[k];
+        g.src_offset[k] = src_offsets[k];
+        g.dst_offset[k] = dst_offsets[k];
+    }
+    if (P_out == 0) return FRG_OK;
+    FRG_HIP(frg::launch_densify_apply(P, P_out, plan, g, noise, params, exp_avg, exp_avg_sq, out_params, out_exp_avg,
+                                      out_exp_avg_sq, (hipStream_t)hip_stream));
+    return FRG_OK;
+}
+
+int frg_reset_opacity(int P, float* raw_opacities, float* exp_avg, float* exp_avg_sq, void* hip_stream)
+{
+    if (P < 0) return fail(FRG_EINVAL, "P < 0");
+    if (P == 0) return FRG_OK;
+    if (!raw_opacities || !exp_avg || !exp_avg_sq) return fail(FRG_EINVAL, "null pointer");
+    FRG_HIP(frg::launch_reset_opacity(P, raw_opacities, exp_avg, exp_avg_sq, (hipStream_t)hip_stream));
+    return FRG_OK;
+}
+
 }  // extern "C"

@@ -199,6 +199,34 @@ hipError_t launch_activate_bwd(int P, const float* opacity, const float* scale, 
 size_t knn_workspace_bytes(int P);
 hipError_t launch_knn(int P, const float* pts, float* out, char* workspace, hipStream_t s);
 
+// adaptive density control over the flat parameter layout (densify.hip)
+#ifndef FRG_DENSIFY_MAX_GROUPS
+#define FRG_DENSIFY_MAX_GROUPS 8
+#endif
+struct DensifyThresholds {
+    float max_grad, min_opacity;
+    float dense_scale;      // percent_dense * extent: above it a selected Gaussian splits, at or below it clones
+    float world_scale;      // 0.1 * extent: the world-size prune, applied when prune_world
+    int prune_world;
+};
+// the per-Gaussian groups of the old and the new flat layout: group 0 = means3D [P,3], 1 = raw scales [P,3], 2 = rotations [P,4],
+// then any others; offsets in elements (multiples of 4), width = elements per Gaussian
+struct DensifyGroups {
+    int count;
+    int width[FRG_DENSIFY_MAX_GROUPS];
+    long long src_offset[FRG_DENSIFY_MAX_GROUPS], dst_offset[FRG_DENSIFY_MAX_GROUPS];
+    long long dst_total;
+};
+hipError_t launch_densify_accumulate(int P, const int* radii, const float* dL_dmean2D, const unsigned char* row_live,
+                                     float* accum, float* denom, float* max_radii2D, hipStream_t s);
+size_t densify_workspace_bytes(int P);
+// plan: int32 [4][P] (destination row per section or -1); record: int32 [8] = nA, nB, nC, nD, P', P, 0, 0
+hipError_t launch_densify_plan(int P, const float* raw_scale, const float* raw_opacity, const float* accum, const float* denom,
+                               const DensifyThresholds& t, int* plan, int* record, char* workspace, hipStream_t s);
+hipError_t launch_densify_apply(int P, int P_out, const int* plan, const DensifyGroups& g, const float* noise, const float* src,
+                                const float* src_m, const float* src_v, float* out, float* out_m, float* out_v, hipStream_t s);
+hipError_t launch_reset_opacity(int P, float* raw_opacity, float* exp_avg, float* exp_avg_sq, hipStream_t s);
+
 // fused photometric loss (photometric.hip)
 size_t photometric_workspace_bytes(int C, int W, int H);
 hipError_t launch_photometric(int C, int W, int H, const float* pred, const float* gt, const float* window11, float lambda,

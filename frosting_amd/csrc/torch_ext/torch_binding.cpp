@@ -28,6 +28,7 @@
 
 #include <string>
 #include <tuple>
+#include <vector>
 
 #include "frosting_rasterizer.h"
 
@@ -331,6 +332,118 @@ torch::Tensor markVisibleHIP(torch::Tensor& means3D, torch::Tensor& viewmatrix, 
     return present;
 }
 
+// ---- adaptive density control (frg_densify_*, frg_reset_opacity): what frosting_amd/densify.py calls through ctypes ----
+namespace {
+
+void check_on(const torch::Tensor& t, const torch::Device& dev, torch::ScalarType type, int64_t numel, const char* name)
+{
+    TORCH_CHECK(t.defined() && t.device() == dev && t.scalar_type() == type && t.is_contiguous() && (numel < 0 || t.numel() == numel),
+                name, ": expected a contiguous ", type, " tensor", numel < 0 ? "" : " of the model's size", " on ", dev);
+}
+
+}  // namespace
+
+void DensifyAccumulateHIP(const torch::Tensor& radii, const torch::Tensor& dL_dmean2D, const torch::Tensor& row_live,
+                          torch::Tensor& xyz_gradient_accum, torch::Tensor& denom, torch::Tensor& max_radii2D)
+{
+    TORCH_CHECK(radii.is_cuda(), "frosting_amd densify: tensors must live on a ROCm device (no CPU path)");
+    const torch::Device dev = radii.device();
+    const c10::hip::HIPGuard guard(dev.index());
+    const int64_t P = radii.numel();
+    check_on(radii, dev, torch::kInt32, P, "radii");
+    check_on(dL_dmean2D, dev, torch::kFloat32, 3 * P, "dL_dmean2D");
+    check_on(xyz_gradient_accum, dev, torch::kFloat32, P, "xyz_gradient_accum");
+    check_on(denom, dev, torch::kFloat32, P, "denom");
+    check_on(max_radii2D, dev, torch::kFloat32, P, "max_radii2D");
+    const bool masked = row_live.defined() && row_live.numel() != 0;
+    if (masked) check_on(row_live, dev, torch::kUInt8, P, "row_live");
+    check_rc(frg_densify_accumulate(static_cast<int>(P), radii.data_ptr<int>(), dL_dmean2D.data_ptr<float>(),
+                                    masked ? row_live.data_ptr<unsigned char>() : nullptr, xyz_gradient_accum.data_ptr<float>(),
+                                    denom.data_ptr<float>(), max_radii2D.data_ptr<float>(),
+                                    c10::hip::getCurrentHIPStream(dev.index()).stream()),
+             "frg_densify_accumulate");
+}
+
+// -> (plan [4,P] int32, record [8] int32 on the device)
+std::tuple<torch::Tensor, torch::Tensor>
+DensifyPlanHIP(const torch::Tensor& raw_scales, const torch::Tensor& raw_opacities, const torch::Tensor& xyz_gradient_accum,
+               const torch::Tensor& denom, const double max_grad, const double min_opacity, const double extent,
+               const double percent_dense, const bool prune_big_points)
+{
+    TORCH_CHECK(raw_scales.is_cuda(), "frosting_amd densify: tensors must live on a ROCm device (no CPU path)");
+    const torch::Device dev = raw_scales.device();
+    const c10::hip::HIPGuard guard(dev.index());
+    const int64_t P = raw_opacities.numel();
+    check_on(raw_scales, dev, torch::kFloat32, 3 * P, "raw_scales");
+    check_on(raw_opacities, dev, torch::kFloat32, P, "raw_opacities");
+    check_on(xyz_gradient_accum, dev, torch::kFloat32, P, "xyz_gradient_accum");
+    check_on(denom, dev, torch::kFloat32, P, "denom");
+    const auto i32 = torch::TensorOptions(torch::kInt32).device(dev);
+    torch::Tensor plan = torch::empty({4, P}, i32), record = torch::empty({8}, i32);
+    const size_t ws_bytes = frg_densify_workspace_bytes(static_cast<int>(P));
+    torch::Tensor workspace = torch::empty({static_cast<int64_t>(ws_bytes ? ws_bytes : 1)}, torch::TensorOptions(torch::kByte).device(dev));
+    frg_densify_params prm{};
+    prm.struct_size = sizeof(prm);
+    prm.max_grad = max_grad; prm.min_opacity = min_opacity; prm.extent = extent; prm.percent_dense = percent_dense;
+    prm.prune_big_points = prune_big_points ? 1 : 0;
+    check_rc(frg_densify_plan(static_cast<int>(P), raw_scales.data_ptr<float>(), raw_opacities.data_ptr<float>(),
+                              xyz_gradient_accum.data_ptr<float>(), denom.data_ptr<float>(), &prm, plan.data_ptr<int>(),
+                              record.data_ptr<int>(), reinterpret_cast<char*>(workspace.data_ptr()), ws_bytes,
+                              c10::hip::getCurrentHIPStream(dev.index()).stream()),
+             "frg_densify_plan");
+    return std::make_tuple(plan, record);
+}
+
+// -> the new (params, exp_avg, exp_avg_sq) flat buffers of out_numel elements
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+DensifyApplyHIP(const torch::Tensor& plan, const int64_t P_out, const std::vector<int64_t>& group_width,
+                const std::vector<int64_t>& src_offsets, const std::vector<int64_t>& dst_offsets, const int64_t out_numel,
+                const torch::Tensor& noise, const torch::Tensor& params, const torch::Tensor& exp_avg, const torch::Tensor& exp_avg_sq)
+{
+    TORCH_CHECK(params.is_cuda(), "frosting_amd densify: tensors must live on a ROCm device (no CPU path)");
+    const torch::Device dev = params.device();
+    const c10::hip::HIPGuard guard(dev.index());
+    TORCH_CHECK(plan.dim() == 2 && plan.size(0) == 4, "plan must be [4, P]");
+    const int64_t P = plan.size(1);
+    check_on(plan, dev, torch::kInt32, 4 * P, "plan");
+    check_on(params, dev, torch::kFloat32, -1, "params");
+    check_on(exp_avg, dev, torch::kFloat32, params.numel(), "exp_avg");
+    check_on(exp_avg_sq, dev, torch::kFloat32, params.numel(), "exp_avg_sq");
+    const bool has_noise = noise.defined() && noise.numel() != 0;
+    if (has_noise) check_on(noise, dev, torch::kFloat32, 6 * P, "noise");
+    const size_t n = group_width.size();
+    TORCH_CHECK(n >= 3 && n <= FRG_DENSIFY_MAX_GROUPS && src_offsets.size() == n && dst_offsets.size() == n, "3 .. 8 groups, one width and two offsets each");
+    int widths[FRG_DENSIFY_MAX_GROUPS];
+    long long so[FRG_DENSIFY_MAX_GROUPS], dof[FRG_DENSIFY_MAX_GROUPS];
+    for (size_t k = 0; k < n; k++) {
+        widths[k] = static_cast<int>(group_width[k]); so[k] = src_offsets[k]; dof[k] = dst_offsets[k];
+        TORCH_CHECK(so[k] >= 0 && so[k] + P * group_width[k] <= params.numel(), "group ", k, " does not lie inside the old buffers");
+    }
+    TORCH_CHECK(out_numel >= 0 && P_out >= 0 && P_out <= 3 * P, "bad output size");
+    const auto f32 = params.options();
+    torch::Tensor out = torch::empty({out_numel}, f32), out_m = torch::empty({out_numel}, f32), out_v = torch::empty({out_numel}, f32);
+    check_rc(frg_densify_apply(static_cast<int>(P), static_cast<int>(P_out), plan.data_ptr<int>(), static_cast<int>(n), widths, so, dof,
+                               out_numel, has_noise ? noise.data_ptr<float>() : nullptr, params.data_ptr<float>(),
+                               exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(), out.data_ptr<float>(), out_m.data_ptr<float>(),
+                               out_v.data_ptr<float>(), c10::hip::getCurrentHIPStream(dev.index()).stream()),
+             "frg_densify_apply");
+    return std::make_tuple(out, out_m, out_v);
+}
+
+void ResetOpacityHIP(torch::Tensor& raw_opacities, torch::Tensor& exp_avg, torch::Tensor& exp_avg_sq)
+{
+    TORCH_CHECK(raw_opacities.is_cuda(), "frosting_amd densify: tensors must live on a ROCm device (no CPU path)");
+    const torch::Device dev = raw_opacities.device();
+    const c10::hip::HIPGuard guard(dev.index());
+    const int64_t P = raw_opacities.numel();
+    check_on(raw_opacities, dev, torch::kFloat32, P, "raw_opacities");
+    check_on(exp_avg, dev, torch::kFloat32, P, "exp_avg");
+    check_on(exp_avg_sq, dev, torch::kFloat32, P, "exp_avg_sq");
+    check_rc(frg_reset_opacity(static_cast<int>(P), raw_opacities.data_ptr<float>(), exp_avg.data_ptr<float>(),
+                               exp_avg_sq.data_ptr<float>(), c10::hip::getCurrentHIPStream(dev.index()).stream()),
+             "frg_reset_opacity");
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.doc() = "MI355X-native Gaussian-splat rasterizer (hand-written gfx950 HIP behind include/frosting_rasterizer.h)";
@@ -341,6 +454,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("rasterize_gaussians_forward_only", &RasterizeGaussiansForwardOnlyHIP);
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansExHIP);
     m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardExHIP);
+    m.def("densify_accumulate", &DensifyAccumulateHIP);
+    m.def("densify_plan", &DensifyPlanHIP);
+    m.def("densify_apply", &DensifyApplyHIP);
+    m.def("reset_opacity", &ResetOpacityHIP);
     m.def("get_option", [](const std::string& name) { return frg_get_option(name.c_str()); });
     m.def("library_version", []() { return frg_version(); });
 }

@@ -41,12 +41,22 @@ class FlatAdam:
     def _build(self, shapes: dict, old=None):
         """(Re)allocate the flat buffers for `shapes`; `old` = (params, exp_avg views, exp_avg_sq views,
         row selector per name) carries state over (densification / pruning)."""
+        _, _, numel = flat_layout(shapes, self.names)
+        flat = torch.zeros(numel, dtype=torch.float32, device=self.device)
+        self._install(shapes, flat, torch.zeros_like(flat), torch.zeros_like(flat))
+        names = self.names
+        if old is not None:
+            for k in names:
+                for dst, src in ((self.params, old[0]), (self.m, old[1]), (self.v, old[2])):
+                    rows = src[k] if old[3] is None else src[k][old[3]]
+                    dst[k][: rows.shape[0]].copy_(rows)
+
+    def _install(self, shapes: dict, flat: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor):
+        """Make the three flat buffers (laid out by flat_layout(shapes)) the optimizer's: layout, views, segment ends."""
         names = self.names
         self.shapes = shapes
         _, self.layout, self.numel = flat_layout(shapes, names)
-        self.flat = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
-        self.exp_avg = torch.zeros_like(self.flat)
-        self.exp_avg_sq = torch.zeros_like(self.flat)
+        self.flat, self.exp_avg, self.exp_avg_sq = flat, exp_avg, exp_avg_sq
         view = lambda buf: {k: buf[o:o + n].view(shapes[k]) for k, (o, n) in self.layout.items()}
         self.params, self.m, self.v = view(self.flat), view(self.exp_avg), view(self.exp_avg_sq)
         # segment k ends where segment k+1 starts (its alignment pad rides along with it, all zeros)
@@ -59,11 +69,20 @@ class FlatAdam:
                 raise ValueError('sh_dc_lr needs a "shs" group of shape [P,K,3]')
             k = names.index("shs")
             self._period[k], self._head[k] = int(shapes["shs"][1] * shapes["shs"][2]), int(shapes["shs"][2])
-        if old is not None:
-            for k in names:
-                for dst, src in ((self.params, old[0]), (self.m, old[1]), (self.v, old[2])):
-                    rows = src[k] if old[3] is None else src[k][old[3]]
-                    dst[k][: rows.shape[0]].copy_(rows)
+
+    def adopt(self, n_rows: int, flat: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor):
+        """Swap in the flat buffers of a model of `n_rows` Gaussians that were written elsewhere (frosting_amd.densify: one
+        kernel writes parameters and both moments of the densified model).  They are laid out by flat_layout with every
+        group's leading dimension replaced by n_rows, alignment pads zero.  `steps` and the learning rates are kept, as
+        the reference keeps state["step"] through densification.  Returns the new params dict."""
+        self._per_gaussian()
+        shapes = {k: (int(n_rows),) + tuple(self.shapes[k][1:]) for k in self.names}
+        _, _, numel = flat_layout(shapes, self.names)
+        for t in (flat, exp_avg, exp_avg_sq):
+            if t.dtype != torch.float32 or t.numel() != numel or not t.is_contiguous() or t.device != self.flat.device or t.dim() != 1:
+                raise RuntimeError(f"adopt: expected contiguous 1-D float32 buffers of {numel} elements on {self.flat.device}")
+        self._install(shapes, flat, exp_avg, exp_avg_sq)
+        return self.params
 
     # ---- densification / pruning (reference: gaussian_model.py _prune_optimizer, cat_tensors_to_optimizer,
     # replace_tensor_to_optimizer; frosting_optimizer.py keeps the same per-group state) -------------------
@@ -264,3 +283,6 @@ class ShardedFlatAdam(FlatAdam):
         raise RuntimeError("ShardedFlatAdam: prune / append re-shard the moments -- not implemented; rebuild the optimizer")
 
     append = prune
+
+    def adopt(self, *args, **kwargs):
+        raise RuntimeError("ShardedFlatAdam: the moments exist per shard only -- buffers of a whole model cannot be adopted")

@@ -554,6 +554,62 @@ int frg_photometric_loss(int channels, int width, int height, const float* image
                          const float* window11, float lambda_dssim, float* loss, float* dL_dimage,
                          char* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* ---- adaptive density control (vanilla 3DGS densification) on the device ------------------------------
+ * Between the backward and the optimizer of the vanilla training loop: add_densification_stats every iteration,
+ * densify_and_prune every 100, reset_opacity every 3000 (gaussian_splatting/train.py:114-124,
+ * gaussian_splatting/scene/gaussian_model.py:210-213, 273-407).  Everything works on the flat layout frg_adam_step
+ * updates, with RAW scales (log) and RAW opacities (logit).  (Additions to version 2: a caller finds out whether a
+ * library has them by looking the symbols up; nothing that existed changed.)
+ *
+ * frg_densify_accumulate (train.py:116-117): for the rows with radii > 0, xyz_gradient_accum += sqrt(gx^2 + gy^2) of
+ * dL_dmean2D [P,3], denom += 1, max_radii2D = max(max_radii2D, radii); all three float32 [P], updated in place; other
+ * rows are not touched.  row_live (optional, as frg_backward_args::row_live leaves it): the gradient row of an unmarked
+ * Gaussian was never written -- it is zero and is not read. */
+int frg_densify_accumulate(int P, const int* radii, const float* dL_dmean2D, const unsigned char* row_live,
+                           float* xyz_gradient_accum, float* denom, float* max_radii2D, void* hip_stream);
+
+/* The thresholds of densify_and_prune(max_grad, min_opacity, extent, max_screen_size) (gaussian_model.py:389) and the
+ * model's percent_dense.  prune_big_points = "max_screen_size is given": the reference's final prune then also drops
+ * rows whose largest scale exceeds 0.1 * extent; its screen-size term reads max_radii2D after densification_postfix
+ * has zeroed it (:345-347, :398) and never fires -- reproduced, so max_screen_size itself has no field. */
+typedef struct frg_densify_params {
+    size_t struct_size;
+    double max_grad, min_opacity, extent, percent_dense;
+    int prune_big_points;
+} frg_densify_params;
+
+/* frg_densify_plan: classify every Gaussian with the reference's float32 arithmetic and comparison directions
+ * (grad = accum / denom, NaN -> 0; clone: grad >= max_grad and max(exp(raw_scale)) <= percent_dense * extent; split: the
+ * same with >; prune of every RESULTING row: sigmoid(raw_opacity) < min_opacity, or, with prune_big_points, its new largest
+ * scale > 0.1 * extent -- a split child's scale is the parent's / 1.6) and place the resulting rows in the reference's order
+ *   [surviving originals | clones | first children of the split rows | second children],  each in source order.
+ * plan: int32 [4][P], the destination row (in the output) of source row i in each of the four sections, or -1;
+ * record: int32 [8] on the device = the four section sizes, P' (their sum), P, 0, 0 -- the caller reads it once to size
+ * the new buffers.  workspace: frg_densify_workspace_bytes(P), 4-byte aligned.  Reads 20 bytes per Gaussian. */
+size_t frg_densify_workspace_bytes(int P);
+int frg_densify_plan(int P, const float* raw_scales, const float* raw_opacities, const float* xyz_gradient_accum,
+                     const float* denom, const frg_densify_params* params, int* plan, int* record,
+                     char* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* frg_densify_apply: one launch that writes the parameters and both Adam moments of the P_out = record[4] resulting rows.
+ * params / exp_avg / exp_avg_sq: the old flat buffers; out_*: freshly allocated ones (every element of the new layout up to
+ * out_numel is written, its alignment pads with zeros).  n_groups per-Gaussian groups (at most FRG_DENSIFY_MAX_GROUPS), the
+ * first three being means3D [P,3], raw scales [P,3], rotations [P,4]; group_width[k] = elements per Gaussian, *_offsets[k] =
+ * where group k starts in the old / new buffers (elements, multiples of 4).  Survivors keep parameter and moment rows;
+ * clones and children get the source's parameter row and zero moments (cat_tensors_to_optimizer, :315-316).  Children
+ * (:358-364, N = 2): xyz' = R(q / |q|) (exp(raw_scale) * z) + xyz, raw_scale' = log(exp(raw_scale) / 1.6), everything else
+ * copied; z = noise[i][child] of noise [P,2,3], standard-normal samples indexed by SOURCE row (may be NULL when no row splits). */
+#define FRG_DENSIFY_MAX_GROUPS 8
+int frg_densify_apply(int P, int P_out, const int* plan, int n_groups, const int* group_width,
+                      const long long* src_offsets, const long long* dst_offsets, long long out_numel, const float* noise,
+                      const float* params, const float* exp_avg, const float* exp_avg_sq,
+                      float* out_params, float* out_exp_avg, float* out_exp_avg_sq, void* hip_stream);
+
+/* frg_reset_opacity (gaussian_model.py:210-213, 258-271): raw_opacity <- logit(min(sigmoid(raw_opacity), 0.01)),
+ * logit(x) = log(x / (1 - x)), and both moments of the opacity segment zeroed; the three pointers are the opacity
+ * segment of the parameter and moment buffers, P elements each. */
+int frg_reset_opacity(int P, float* raw_opacities, float* exp_avg, float* exp_avg_sq, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
