@@ -1,14 +1,12 @@
-// C ABI of libfrosting_rasterizer.so (include/frosting_rasterizer.h): host-side
+// C ABI of libfrosting_rasterizer.so (include/frosting_rasterizer.h), the rasterizer: host-side
 // orchestration of the forward / backward kernel sequence on the caller's HIP
 // stream.  Mirrors the reference's Rasterizer::forward / backward control flow
 // (rasterizer_impl.cu:198-336, :340-434) -- one blocking 48-byte read-back for
-// num_rendered, everything else asynchronous.
-#include "../../include/frosting_rasterizer.h"
-#include "kernels.h"
+// num_rendered, everything else asynchronous.  The other entry points are in api_ops.hip.
+#include "host_common.h"
 
 #include <algorithm>
 #include <atomic>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -18,6 +16,25 @@
 #include <mutex>
 #include <optional>
 #include <thread>
+
+// ---- the error record ---------------------------------------------------------
+static thread_local char g_err[512] = "";
+
+int frg::fail(int code, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+using frg::cpu_relax;
+using frg::fail;
+
+// ---- options ------------------------------------------------------------------
+// the stages of frg_stage_times (option "profile_stage" names one)
+enum { ST_PREPROCESS = 0, ST_SCAN, ST_SCATTER, ST_SORT, ST_BLEND_FWD, ST_BLEND_BWD, ST_PREPROCESS_BWD, ST_SH_COLOR, ST_COUNT };
 
 // the options the launchers read (declared in kernels.h)
 namespace frg {
@@ -30,29 +47,6 @@ std::atomic<int> g_combine_blocks{0};   // 3, 6, 12 or 24 are the useful values;
 }  // namespace frg
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-// spin-wait hint of the mailbox polls (the host side is not tied to x86)
-inline void cpu_relax()
-{
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__) || defined(__arm__)
-    __asm__ __volatile__("yield");
-#else
-    __asm__ __volatile__("" ::: "memory");
-#endif
-}
-
-int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 std::atomic<int> g_exact_blend{-1};
 std::atomic<int> g_profile{0};
@@ -73,11 +67,72 @@ std::atomic<int> g_probe{0};
 // TEST HOOK (FROSTING_EXPERIMENTS=1): pretend every forward posted "no heavy waves", so that the backward skips the 16-wave
 // launch of the per-Gaussian backward whatever the geometry holds -- the plain kernel's safety net must then do that work
 std::atomic<int> g_assume_no_heavy{0};
+std::atomic<int> g_use_mailbox{1};
+std::atomic<int> g_sh_no_dir{0};           // option "sh_dir_in_backward"
+std::atomic<int> g_fwd_unroll8{1};         // option "fwd_unroll8": 0 never | 1 frames of a few long lists (the host's rule) | 2 always
+std::atomic<int> g_fused_small{1};         // option "fused_small": frames of at most 2^20 instances sort their short lists inside the forward blend
+std::atomic<int> g_sparse_sh{1};            // option "sparse_sh": the SH pass over the visible Gaussians only, where a view sees a part of the model
+std::atomic<int> g_bwd_heavy_first{1};
+std::atomic<int> g_clear_image_state{0};   // 1: the memset in front of every forward, needed or not
 
+// Every option of frg_set_option / frg_get_option: its name, where its value lives, what is stored for a requested value.
+// Experiment knobs ("ablate" and "probe" make kernels skip work or ignore dependencies: WRONG results) can be set only in a
+// process started with FROSTING_EXPERIMENTS=1, so that a stray call cannot switch them on, and do not answer frg_get_option.
+struct Option {
+    const char* name;
+    std::atomic<int>* value;
+    int (*stored)(int requested);
+    bool experiment;
+};
+int as_flag(int v) { return v ? 1 : 0; }
+int not_negative(int v) { return v < 0 ? 0 : v; }
+const Option kOptions[] = {
+    {"exact_blend", &g_exact_blend, as_flag, false},     // (unset until first asked for: FROSTING_EXACT_BLEND, exact_blend())
+    {"profile", &g_profile, as_flag, false},
+    {"profile_stage", &g_profile_stage, [](int v) { return v < 0 || v >= ST_COUNT ? -1 : v; }, false},
+    {"global_bins", &g_global_bins, as_flag, false},
+    {"tight_binning", &g_tight_binning, as_flag, false},
+    {"bwd_batch", &g_bwd_batch, [](int v) { return v == 2 ? 2 : 3; }, false},
+    {"bwd_seg_log", &g_bwd_seg_log, [](int v) { return v >= FRG_BWD_SEG_LOG_MIN && v <= FRG_BWD_SEG_LOG_MAX ? v : 0; }, false},
+    {"counter_mailbox", &g_use_mailbox, as_flag, false},
+    {"sparse_sh", &g_sparse_sh, as_flag, false},
+    {"fwd_prefetch", &frg::g_fwd_prefetch, as_flag, false},
+    {"bwd_heavy_first", &g_bwd_heavy_first, as_flag, false},
+    {"bwd_waves", &frg::g_bwd_waves, not_negative, false},
+    {"fwd_order", &frg::g_fwd_order, as_flag, false},
+    {"sh_dir_in_backward", &g_sh_no_dir, as_flag, false},
+    {"clear_image_state", &g_clear_image_state, as_flag, false},
+    {"sort_heavy_on_caller", &frg::g_sort_heavy_on_caller, as_flag, false},
+    {"async_sh", &g_async_sh, [](int v) { return v < 0 || v > 3 ? 1 : v; }, false},
+    {"fused_small", &g_fused_small, as_flag, false},
+    {"fwd_unroll8", &g_fwd_unroll8, [](int v) { return v < 0 || v > 2 ? 1 : v; }, false},
+    {"combine_blocks", &frg::g_combine_blocks, not_negative, false},
+    {"ablate", &g_ablate, [](int v) { return v; }, true},
+    {"probe", &g_probe, [](int v) { return v; }, true},
+    {"assume_no_heavy", &g_assume_no_heavy, as_flag, true},
+    {"rows_grid", &frg::g_rows_grid, [](int v) { return v <= 0 ? 0 : v < 8 ? 8 : v; }, true},
+};
+const Option* find_option(const char* name)
+{
+    for (const Option& o : kOptions) if (name && strcmp(name, o.name) == 0) return &o;
+    return nullptr;
+}
+
+int exact_blend()
+{
+    int v = g_exact_blend.load();
+    if (v < 0) {
+        const char* e = getenv("FROSTING_EXACT_BLEND");
+        v = (e && e[0] == '1') ? 1 : 0;
+        g_exact_blend.store(v);
+    }
+    return v;
+}
+
+// ---- stage timers -------------------------------------------------------------
 // Optional per-stage GPU timing (frg_set_option("profile", 1)): hipEvents are
 // recorded on the caller's stream between the kernels of one forward / backward;
 // frg_stage_times() synchronises and returns the elapsed milliseconds.
-enum { ST_PREPROCESS = 0, ST_SCAN, ST_SCATTER, ST_SORT, ST_BLEND_FWD, ST_BLEND_BWD, ST_PREPROCESS_BWD, ST_SH_COLOR, ST_COUNT };
 // Event pairs are kept for the last ST_SLOTS launches of every stage and only read (and
 // synchronised on) by frg_stage_times(), so timing a run of steps does not serialise them.
 constexpr int ST_SLOTS = 64;
@@ -128,17 +183,7 @@ struct StageScope {
     }
 };
 
-int exact_blend()
-{
-    int v = g_exact_blend.load();
-    if (v < 0) {
-        const char* e = getenv("FROSTING_EXACT_BLEND");
-        v = (e && e[0] == '1') ? 1 : 0;
-        g_exact_blend.store(v);
-    }
-    return v;
-}
-
+// ---- what the host keeps between calls, per thread and per process ------------
 // One pinned landing pad per host thread for the counters read-back.
 frg::Counters* pinned_counters()
 {
@@ -151,6 +196,7 @@ frg::Counters* pinned_counters()
 
 // Deferred-counters forward: the counters of each outstanding forward land in a pinned slot
 // behind an event; frg_forward_finish() waits on that event only (not on the whole stream).
+// Per host thread: a deferred forward is finished by the thread that started it.
 struct PendingCounters {
     frg::Counters* host = nullptr;     // pinned
     hipEvent_t ev = nullptr;           // counters have landed in `host`
@@ -220,22 +266,15 @@ struct HostMail {
     }
 };
 thread_local HostMail g_mail;
-std::atomic<int> g_use_mailbox{1};
-std::atomic<int> g_sh_no_dir{0};           // option "sh_dir_in_backward"
-std::atomic<int> g_fwd_unroll8{1};         // option "fwd_unroll8": 0 never | 1 frames of a few long lists (the host's rule) | 2 always
-std::atomic<int> g_fused_small{1};         // option "fused_small": frames of at most 2^20 instances sort their short lists inside the forward blend
-std::atomic<int> g_sparse_sh{1};            // option "sparse_sh": the SH pass over the visible Gaussians only, where a view sees a part of the model
-std::atomic<int> g_bwd_heavy_first{1};
-std::atomic<int> g_clear_image_state{0};   // 1: the memset in front of every forward, needed or not
 
 // What the host remembers about the forward that last filled a geometry buffer (process-wide: autograd runs the backward
 // on another thread than the forward): which mailbox post is its scatter's, how many instances it rendered, whether it was
 // told that no backward follows.  Scheduling hints and early refusals only -- keyed by ADDRESS, a note can be stale (a buffer
 // copied to an address an earlier forward used), so nothing that decides a gradient bit hangs on one: the blend arithmetic
 // and "nothing kept" are stamped into the image chunk by the forward's blend kernel (Counters::fwd_flags) and read there
-// (backward_impl).  A ring of kFwdNotes entries (the entry of the same address is overwritten, else the next ring slot); a
-// forgotten forward's note reads "unknown" everywhere (rendered -1, forward_only settled by the stamp, both forms of the
-// per-Gaussian backward launched as if nothing had been posted).  The pinned mailboxes are never freed.
+// (settle_forward_stamp).  A ring of kFwdNotes entries (the entry of the same address is overwritten, else the next ring
+// slot); a forgotten forward's note reads "unknown" everywhere (rendered -1, forward_only settled by the stamp, both forms
+// of the per-Gaussian backward launched as if nothing had been posted).  The pinned mailboxes are never freed.
 struct FwdNote {
     const void* geom = nullptr; const frg::Mailbox* mail = nullptr; uint32_t seq = 0; int exact = -1; int rendered = -1; bool fwd_only = false;
     // -> the number of heavy waves the forward's scatter posted, or -1 when unknown (no post, not arrived yet, the mailbox
@@ -257,9 +296,9 @@ struct FwdNote {
         }
     }
 };
-std::mutex g_heavy_mu;
 class FwdNotes {
     static constexpr int kFwdNotes = 1024;
+    std::mutex mu;
     FwdNote ring[kFwdNotes];
     unsigned next = 0;
     FwdNote* locate(const void* geom)
@@ -271,7 +310,7 @@ public:
     // a forward starts on `geom`: whatever an earlier forward posted about this buffer is void now
     void begin(const void* geom, int exact, bool fwd_only)
     {
-        std::lock_guard<std::mutex> lk(g_heavy_mu);
+        std::lock_guard<std::mutex> lk(mu);
         FwdNote* n = locate(geom);
         *(n ? n : &ring[next++ % kFwdNotes]) = FwdNote{geom, nullptr, 0, exact, -1, fwd_only};
     }
@@ -279,13 +318,13 @@ public:
     template <class Fn>
     void update(const void* geom, Fn fn)
     {
-        std::lock_guard<std::mutex> lk(g_heavy_mu);
+        std::lock_guard<std::mutex> lk(mu);
         if (FwdNote* n = locate(geom)) fn(*n);
     }
     // -> a copy of the note of the forward that last filled `geom`; nothing when that forward is not remembered
     std::optional<FwdNote> find(const void* geom)
     {
-        std::lock_guard<std::mutex> lk(g_heavy_mu);
+        std::lock_guard<std::mutex> lk(mu);
         const FwdNote* n = locate(geom);
         return n ? std::optional<FwdNote>(*n) : std::nullopt;
     }
@@ -293,30 +332,51 @@ public:
 FwdNotes g_fwd_notes;
 
 // Two-call backward (frg_backward_args::phase): phase 2 reads the nine per-Gaussian sums phase 1 left in the workspace.
-// What phase 1 was called with is remembered per workspace pointer; a phase 2 that does not match (an arena that grew or
-// was reused between the calls, another frame's buffers) is refused instead of producing garbage gradients.
-struct PhaseNote { const void* workspace = nullptr; const void* geom = nullptr; const void* image = nullptr; int P = 0, R = 0; };
-constexpr int kPhaseNotes = 16;
-PhaseNote g_phase_notes[kPhaseNotes];
-unsigned g_phase_next = 0;
-void note_phase1(const void* workspace, const void* geom, const void* image, int P, int R)
-{
-    std::lock_guard<std::mutex> lk(g_heavy_mu);
-    for (auto& n : g_phase_notes) if (n.workspace == workspace) { n = PhaseNote{workspace, geom, image, P, R}; return; }
-    g_phase_notes[g_phase_next++ % kPhaseNotes] = PhaseNote{workspace, geom, image, P, R};
-}
-bool phase1_matches(const void* workspace, const void* geom, const void* image, int P, int R)
-{
-    std::lock_guard<std::mutex> lk(g_heavy_mu);
-    for (auto& n : g_phase_notes)
-        if (n.workspace == workspace) {
-            const bool ok = n.geom == geom && n.image == image && n.P == P && n.R == R;
-            n = PhaseNote{};      // the sums are consumed once
-            return ok;
-        }
-    return false;
-}
+// What phase 1 was called with is remembered per workspace pointer (process-wide, a ring of kPhaseNotes); a phase 2 that
+// does not match (an arena that grew or was reused between the calls, another frame's buffers) is refused instead of
+// producing garbage gradients.  A note decides that refusal and nothing else.
+class PhaseNotes {
+    struct Note { const void* workspace = nullptr; const void* geom = nullptr; const void* image = nullptr; int P = 0, R = 0; };
+    static constexpr int kPhaseNotes = 16;
+    std::mutex mu;
+    Note ring[kPhaseNotes];
+    unsigned next = 0;
+public:
+    // phase 1 ran on `workspace`
+    void record(const void* workspace, const void* geom, const void* image, int P, int R)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto& n : ring) if (n.workspace == workspace) { n = Note{workspace, geom, image, P, R}; return; }
+        ring[next++ % kPhaseNotes] = Note{workspace, geom, image, P, R};
+    }
+    // -> phase 1 ran on `workspace` with these arguments; the sums are consumed once
+    bool consume(const void* workspace, const void* geom, const void* image, int P, int R)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto& n : ring)
+            if (n.workspace == workspace) {
+                const bool ok = n.geom == geom && n.image == image && n.P == P && n.R == R;
+                n = Note{};
+                return ok;
+            }
+        return false;
+    }
+};
+PhaseNotes g_phase_notes;
 
+// Side streams (frg::SideStream, kernels.h), one per host thread each:
+// the deferred SH colour kernel's (fork: the geometry is there | join: the colours are).  Lowest priority: the colour
+// kernel floods every CU with streaming waves; the small latency-bound kernels of the binning stages on the caller's
+// stream must win the arbitration
+thread_local frg::SideStream g_sh_side{frg::SideStream::LOWEST};
+// the timing experiments' ("probe")
+thread_local frg::SideStream g_probe_side{frg::SideStream::DEFAULT};
+// the per-Gaussian backward's 16-wave launch's.  HIGHEST priority: the 16-wave workgroups need a whole CU's LDS each; both
+// launches become ready when the blend backward ends, and unless the dispatcher places these first they wait until the
+// plain kernel has drained (rocprofv3, round 3: 274 us "duration" for a launch whose workgroups found an empty list)
+thread_local frg::SideStream g_bwd_side{frg::SideStream::HIGHEST};
+
+// ---- helpers of both directions -----------------------------------------------
 // Spin until the kernel's post arrives.  false: the stream failed, or it drained without the post becoming visible.
 bool mailbox_wait(const uint32_t* flag, uint32_t seq, hipStream_t stream)
 {
@@ -334,31 +394,6 @@ bool mailbox_wait(const uint32_t* flag, uint32_t seq, hipStream_t stream)
     }
 }
 
-// Side streams (frg::SideStream, kernels.h), one per host thread each:
-// the deferred SH colour kernel's (fork: the geometry is there | join: the colours are).  Lowest priority: the colour
-// kernel floods every CU with streaming waves; the small latency-bound kernels of the binning stages on the caller's
-// stream must win the arbitration
-thread_local frg::SideStream g_sh_side{frg::SideStream::LOWEST};
-// the timing experiments' ("probe")
-thread_local frg::SideStream g_probe_side{frg::SideStream::DEFAULT};
-// the per-Gaussian backward's 16-wave launch's.  HIGHEST priority: the 16-wave workgroups need a whole CU's LDS each; both
-// launches become ready when the blend backward ends, and unless the dispatcher places these first they wait until the
-// plain kernel has drained (rocprofv3, round 3: 274 us "duration" for a launch whose workgroups found an empty list)
-thread_local frg::SideStream g_bwd_side{frg::SideStream::HIGHEST};
-
-// a negative return code leaves the function
-#define FRG_TRY(expr)                  \
-    do {                               \
-        const int rc_ = (expr);        \
-        if (rc_ < 0) return rc_;       \
-    } while (0)
-
-#define FRG_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return fail(FRG_EHIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
 // debug mode: synchronise after every stage so a faulting kernel is attributed
 // (the reference's CHECK_CUDA, auxiliary.h:166-173)
 #define FRG_STAGE(call, name)                                                                               \
@@ -374,12 +409,10 @@ struct FwdModes {
     int fwd_only = 0;     // frg_forward_args::forward_only (per call only: there is no process-wide form)
     static int pick(int field, int max_value, int fallback) { return field >= 1 && field <= max_value + 1 ? field - 1 : fallback; }
 };
-int exact_blend();
-FwdModes default_modes();
+FwdModes default_modes() { return FwdModes{exact_blend(), g_tight_binning.load(), g_async_sh.load(), 0}; }
 
-frg::ViewParams make_view(int P, int D, int M, int width, int height, float tan_fovx, float tan_fovy, float scale_modifier, int tight)
+frg::ViewParams make_view(int D, int M, int width, int height, float tan_fovx, float tan_fovy, float scale_modifier, int tight)
 {
-    (void)P;
     frg::ViewParams vp;
     vp.tan_fovx = tan_fovx; vp.tan_fovy = tan_fovy;
     vp.focal_y = height / (2.0f * tan_fovy);  // rasterizer_impl.cu:222-223
@@ -394,8 +427,6 @@ frg::ViewParams make_view(int P, int D, int M, int width, int height, float tan_
     return vp;
 }
 
-FwdModes default_modes() { return FwdModes{exact_blend(), g_tight_binning.load(), g_async_sh.load(), 0}; }
-
 // frg_forward_args / frg_backward_args grew field by field: a caller built against an earlier header states a smaller
 // struct_size.  One of the accepted generation sizes: *full <- the caller's bytes, the fields it does not know zeroed --
 // every field added after the first generation reads 0 / NULL as "absent / the process default / one call".
@@ -408,47 +439,526 @@ bool widen(const Args* a, std::initializer_list<size_t> generations, Args* full)
     return true;
 }
 
-// Every option of frg_set_option / frg_get_option: its name, where its value lives, what is stored for a requested value.
-// Experiment knobs ("ablate" and "probe" make kernels skip work or ignore dependencies: WRONG results) can be set only in a
-// process started with FROSTING_EXPERIMENTS=1, so that a stray call cannot switch them on, and do not answer frg_get_option.
-struct Option {
-    const char* name;
-    std::atomic<int>* value;
-    int (*stored)(int requested);
-    bool experiment;
-};
-int as_flag(int v) { return v ? 1 : 0; }
-int not_negative(int v) { return v < 0 ? 0 : v; }
-const Option kOptions[] = {
-    {"exact_blend", &g_exact_blend, as_flag, false},     // (unset until first asked for: FROSTING_EXACT_BLEND, exact_blend())
-    {"profile", &g_profile, as_flag, false},
-    {"profile_stage", &g_profile_stage, [](int v) { return v < 0 || v >= ST_COUNT ? -1 : v; }, false},
-    {"global_bins", &g_global_bins, as_flag, false},
-    {"tight_binning", &g_tight_binning, as_flag, false},
-    {"bwd_batch", &g_bwd_batch, [](int v) { return v == 2 ? 2 : 3; }, false},
-    {"bwd_seg_log", &g_bwd_seg_log, [](int v) { return v >= FRG_BWD_SEG_LOG_MIN && v <= FRG_BWD_SEG_LOG_MAX ? v : 0; }, false},
-    {"counter_mailbox", &g_use_mailbox, as_flag, false},
-    {"sparse_sh", &g_sparse_sh, as_flag, false},
-    {"fwd_prefetch", &frg::g_fwd_prefetch, as_flag, false},
-    {"bwd_heavy_first", &g_bwd_heavy_first, as_flag, false},
-    {"bwd_waves", &frg::g_bwd_waves, not_negative, false},
-    {"fwd_order", &frg::g_fwd_order, as_flag, false},
-    {"sh_dir_in_backward", &g_sh_no_dir, as_flag, false},
-    {"clear_image_state", &g_clear_image_state, as_flag, false},
-    {"sort_heavy_on_caller", &frg::g_sort_heavy_on_caller, as_flag, false},
-    {"async_sh", &g_async_sh, [](int v) { return v < 0 || v > 3 ? 1 : v; }, false},
-    {"fused_small", &g_fused_small, as_flag, false},
-    {"fwd_unroll8", &g_fwd_unroll8, [](int v) { return v < 0 || v > 2 ? 1 : v; }, false},
-    {"combine_blocks", &frg::g_combine_blocks, not_negative, false},
-    {"ablate", &g_ablate, [](int v) { return v; }, true},
-    {"probe", &g_probe, [](int v) { return v; }, true},
-    {"assume_no_heavy", &g_assume_no_heavy, as_flag, true},
-    {"rows_grid", &frg::g_rows_grid, [](int v) { return v <= 0 ? 0 : v < 8 ? 8 : v; }, true},
-};
-const Option* find_option(const char* name)
+// the raw-parameter fields, named alike in frg_forward_args and frg_backward_args
+template <class Args>
+frg::RawInputs raw_inputs_of(const Args& a)
 {
-    for (const Option& o : kOptions) if (name && strcmp(name, o.name) == 0) return &o;
-    return nullptr;
+    frg::RawInputs rw;
+    rw.raw_opacity = a.raw_opacities; rw.raw_scale = a.raw_scales; rw.raw_rot = a.raw_rotations;
+    rw.shell_logits = a.shell_logits; rw.shell_verts = a.shell_cell_verts; rw.shell_cells = a.shell_cells;
+    rw.bary_mode = a.shell_bary_mode;
+    return rw;
+}
+
+// ---- forward ------------------------------------------------------------------
+// The argument checks of a forward, in the order their messages are promised.  An empty model (P == 0) needs nothing
+// beyond sizes and out_color: the checks behind that line are not made for it.
+int validate_forward(const frg_forward_args& a)
+{
+    if (a.instance_capacity < 0) return fail(FRG_EINVAL, "instance_capacity < 0");
+    if (a.forward_only < 0 || a.forward_only > 1) return fail(FRG_EINVAL, "frg_forward_args: forward_only must be 0 or 1");
+    if (a.forward_only && a.instance_capacity > 0)
+        return fail(FRG_EINVAL, "frg_forward_args: forward_only with deferred counters (instance_capacity > 0) is not offered");
+    if (a.exact_blend < 0 || a.exact_blend > 2 || a.tight_binning < 0 || a.tight_binning > 2 || a.async_sh < 0 ||
+        a.async_sh > 4 || a.shell_bary_mode < 0 || a.shell_bary_mode > 1)
+        return fail(FRG_EINVAL, "frg_forward_args: mode out of range (exact_blend %d, tight_binning %d, async_sh %d, shell_bary_mode %d)",
+                    a.exact_blend, a.tight_binning, a.async_sh, a.shell_bary_mode);
+    if (a.P < 0 || a.width <= 0 || a.height <= 0) return fail(FRG_EINVAL, "bad sizes P=%d W=%d H=%d", a.P, a.width, a.height);
+    if (!a.out_color) return fail(FRG_EINVAL, "out_color is null");
+    if (a.P == 0) return FRG_OK;
+    if (!a.viewmatrix || !a.projmatrix || !a.cam_pos || !a.background) return fail(FRG_EINVAL, "null required pointer");
+    if ((a.means3D == nullptr) == (a.shell_logits == nullptr))
+        return fail(FRG_EINVAL, "provide exactly one of means3D / shell_logits");
+    if (a.shell_logits && (!a.shell_cell_verts || !a.shell_cells))
+        return fail(FRG_EINVAL, "shell_logits needs shell_cell_verts and shell_cells");
+    if ((a.opacities == nullptr) == (a.raw_opacities == nullptr))
+        return fail(FRG_EINVAL, "provide exactly one of opacities / raw_opacities");
+    if ((a.shs == nullptr) == (a.colors_precomp == nullptr))
+        return fail(FRG_EINVAL, "provide exactly one of shs / colors_precomp");
+    if ((a.raw_scales == nullptr) != (a.raw_rotations == nullptr))
+        return fail(FRG_EINVAL, "raw_scales and raw_rotations come together");
+    const bool have_sr = (a.scales && a.rotations) || a.raw_scales;
+    if ((a.scales || a.rotations) && a.raw_scales) return fail(FRG_EINVAL, "provide (scales, rotations) or their raw forms, not both");
+    if (((a.scales == nullptr) != (a.rotations == nullptr)) || have_sr == (a.cov3D_precomp != nullptr))
+        return fail(FRG_EINVAL, "provide exactly one of (scales, rotations) / cov3D_precomp");
+    if (a.shs && (a.D < 0 || a.D > 3 || a.M < (a.D + 1) * (a.D + 1)))
+        return fail(FRG_EINVAL, "SH degree %d needs %d coefficients, got M=%d", a.D, (a.D + 1) * (a.D + 1), a.M);
+    if (!a.geometry_alloc || !a.binning_alloc || !a.image_alloc) return fail(FRG_EINVAL, "null allocation callback");
+    return FRG_OK;
+}
+
+struct FwdCtx;
+// SH colours: nothing before the blend needs them, and the stages in between (scan, scatter, sort) leave the
+// HBM nearly idle -- the colour kernel (the largest single stream of the forward, 192 B per visible Gaussian)
+// runs beside them on this thread's side stream (g_sh_side); the blend joins it.  An error return between the fork
+// and the join must not leave the side kernel running on the caller's inputs: the destructor waits for it.
+class ShFork {
+    int mode = 0;      // 0 inside preprocess | side stream forked after: 1 preprocess, 2 scan, 3 scatter
+    bool forked = false, joined = false;
+public:
+    ShFork() = default;
+    ShFork(const ShFork&) = delete;
+    ~ShFork() { if (forked && !joined) (void)hipStreamSynchronize(g_sh_side.stream); }
+    void arm(int sh_mode) { mode = sh_mode != 0 && g_sh_side.ensure() ? sh_mode : 0; }
+    bool deferred() const { return mode != 0; }
+    // stage `at` has been enqueued: launches the colour kernel if this is the stage it was to follow (at the latest after the scatter)
+    int fork(int at, const FwdCtx& x);
+    // the caller's stream waits for the colours
+    int join(hipStream_t stream)
+    {
+        if (!deferred()) return FRG_OK;
+        FRG_HIP(hipStreamWaitEvent(stream, g_sh_side.join, 0));
+        joined = true;
+        return FRG_OK;
+    }
+};
+
+// What the steps of one forward share.
+struct FwdCtx {
+    const frg_forward_args& a;
+    FwdModes md;
+    int debug;            // (deferred counters: no synchronisation, the stage-by-stage one included)
+    int seg_forced;       // option "bwd_seg_log", read once: the size asked of the callback and the carve must agree
+    hipStream_t stream;
+    frg::ViewParams vp;
+    int T, index_bits;    // tiles | bits needed for a Gaussian index
+    char *geom_chunk, *img_chunk;
+    frg::GeomState g;
+    frg::ImageState img;
+    int* radii;
+    frg::FwdInputs in;
+    ShFork sh;
+    // the binning chunk of R instances whose longest tile list has `longest` entries, from the caller's callback
+    int alloc_binning(int R, int longest, frg::BinningState* b) const
+    {
+        char* bin_chunk = a.binning_alloc(a.user, frg::BinningState::carve(nullptr, R, longest, seg_forced).bytes);
+        if (!bin_chunk) return fail(FRG_EALLOC, "binning allocation callback returned null");
+        *b = frg::BinningState::carve(bin_chunk, R, longest, seg_forced);
+        return FRG_OK;
+    }
+    hipError_t blend(const frg::BinningState& b, bool fwd_only, bool fused_sort, bool long_lists) const
+    {
+        return (md.exact ? frg::launch_blend_fwd_exact : frg::launch_blend_fwd_fast)(vp, g, img, b, a.background, a.out_color, stream, fwd_only,
+                                                                                     fused_sort, long_lists);
+    }
+};
+
+int ShFork::fork(int at, const FwdCtx& x)
+{
+    if (!deferred() || forked || (at < mode && at < 3)) return FRG_OK;
+    forked = true;
+    FRG_HIP(g_sh_side.fork_from(x.stream));
+    {
+        StageScope sc_(ST_SH_COLOR, g_sh_side.stream);
+        FRG_HIP(frg::launch_sh_color(x.a.P, x.vp, x.in, x.radii, x.g, g_sh_side.stream));
+    }
+    FRG_HIP(hipEventRecord(g_sh_side.join, g_sh_side.stream));
+    if (x.debug) FRG_HIP(hipStreamSynchronize(g_sh_side.stream));
+    return FRG_OK;
+}
+
+// LDS-bins paths: nothing of the image chunk needs clearing in front of the forward -- colsum_kernel zeroes the
+// scatter cursors and the blend's depth marks on its way, every counter is written unconditionally; only the flag
+// of the prefiltered assertion is set-only.  Global bins (more tiles than the LDS holds): the per-tile counts are
+// accumulated with atomics, the whole region is cleared.
+int clear_image_state(const FwdCtx& x)
+{
+    const frg::ImageState& img = x.img;
+    if (!img.lds_bins || g_clear_image_state.load(std::memory_order_relaxed)) FRG_HIP(hipMemsetAsync(x.img_chunk + img.zero_begin, 0, img.zero_bytes, x.stream));
+    else if (x.a.prefiltered || x.a.instance_capacity > 0) FRG_HIP(hipMemsetAsync(&img.counters->filtered, 0, sizeof(uint32_t), x.stream));   // (deferred: frg_forward_finish is told `prefiltered` again)
+    return FRG_OK;
+}
+
+int stage_preprocess(FwdCtx& x)
+{
+    const int debug = x.debug;
+    hipStream_t stream = x.stream;
+    { StageScope sc_(ST_PREPROCESS, stream); FRG_STAGE(frg::launch_preprocess_fwd(x.a.P, x.vp, x.in, x.radii, x.g, x.img, x.a.prefiltered, x.sh.deferred(), stream), "preprocess"); }
+    return x.sh.fork(1, x);
+}
+
+// mail (optional): where the scan workgroups post the counters for the polling host thread
+int stage_scan(FwdCtx& x, frg::Mailbox* mail, uint32_t mail_seq)
+{
+    const int debug = x.debug;
+    hipStream_t stream = x.stream;
+    { StageScope sc_(ST_SCAN, stream); FRG_STAGE(frg::launch_scan(x.a.P, x.vp, x.g, x.img, (uint32_t)x.a.instance_capacity, stream, mail, mail_seq), "scan"); }
+    return x.sh.fork(2, x);
+}
+
+// instance_capacity > 0: no host synchronisation at all -- the binning buffer is sized for `capacity` instances up
+// front, launches that depend on the counters use device-side values, and the counters travel to a pinned slot that
+// frg_forward_finish() inspects later.  Everything is enqueued without knowing R on the host; the 48-byte read-back
+// rides a side stream so that no later kernel queues behind it.
+int forward_deferred(FwdCtx& x)
+{
+    const int capacity = x.a.instance_capacity, debug = x.debug, T = x.T;
+    hipStream_t stream = x.stream;
+    const frg::ImageState& img = x.img;
+    bool reused = false;
+    PendingCounters* pend = g_pending.acquire(x.img_chunk, &reused);
+    if (!pend) return fail(FRG_EHIP, "pinned counter slot / event creation failed");
+    // the previous deferred forward on this image buffer reads its counters back on a side stream:
+    // that copy must have happened before the counters are cleared again
+    if (reused) FRG_HIP(hipStreamWaitEvent(stream, pend->ev, 0));
+    FRG_TRY(clear_image_state(x));
+    FRG_TRY(stage_preprocess(x));
+    FRG_TRY(stage_scan(x, nullptr, 0));
+    FRG_HIP(hipEventRecord(pend->scanned, stream));
+    FRG_HIP(hipStreamWaitEvent(pend->copy_stream, pend->scanned, 0));
+    FRG_HIP(hipMemcpyAsync(pend->host, img.counters, sizeof(frg::Counters), hipMemcpyDeviceToHost, pend->copy_stream));
+    FRG_HIP(hipEventRecord(pend->ev, pend->copy_stream));
+    frg::BinningState b;
+    FRG_TRY(x.alloc_binning(capacity, FRG_SORT_LDS_CAP + 1, &b));
+    FRG_STAGE(frg::launch_sort_plan(T, nullptr, img.counters->class_count, img.class_tiles, img.ranges, b.big_plan, (uint32_t)capacity, stream), "sort plan");
+    { StageScope sc_(ST_SCATTER, stream); FRG_STAGE(frg::launch_scatter(x.a.P, x.vp, x.radii, x.g, img, b, stream, g_ablate.load()), "scatter"); }
+    FRG_TRY(x.sh.fork(3, x));
+    { StageScope sc_(ST_SORT, stream); FRG_STAGE(frg::launch_tile_sort(T, nullptr, g_pending.have_hint ? g_pending.last_class_count : nullptr, img.counters->class_count, img.class_tiles, img.ranges, b.pairs, b.pairs_tmp, b.big_hist, b.big_plan, (uint32_t)capacity, 0, x.index_bits, b.point_list, stream), "sort"); }
+    FRG_TRY(x.sh.join(stream));
+    StageScope sc_(ST_BLEND_FWD, stream);
+    FRG_STAGE(x.blend(b, false, false, false), "blend");
+    return capacity;
+}
+
+// The mailbox's first post said how many instances the frame has: the binning buffer is sized for every sort path -- the
+// longest tile list is not known yet -- and the scatter is enqueued while the reorder still runs.
+int scatter_early(FwdCtx& x, int R, frg::Mailbox* mail, uint32_t mail_seq, frg::BinningState* b)
+{
+    const int debug = x.debug;
+    hipStream_t stream = x.stream;
+    const frg::ImageState& img = x.img;
+    FRG_TRY(x.alloc_binning(R, FRG_SORT_LDS_CAP + 1, b));
+    if (g_mail.long_lists)
+        FRG_STAGE(frg::launch_sort_plan(x.T, nullptr, img.counters->class_count, img.class_tiles, img.ranges, b->big_plan, (uint32_t)R, stream, 1), "sort plan");
+    { StageScope sc_(ST_SCATTER, stream); FRG_STAGE(frg::launch_scatter(x.a.P, x.vp, x.radii, x.g, img, *b, stream, g_ablate.load(), mail, mail_seq), "scatter"); }
+    FRG_TRY(x.sh.fork(3, x));
+    g_fwd_notes.update(x.geom_chunk, [&](FwdNote& n) { n.mail = mail; n.seq = mail_seq; });
+    g_mail.last_P = x.a.P; g_mail.last_seq = mail_seq;
+    return FRG_OK;
+}
+
+// The one place that yields the host's copy of a blocking forward's counters: the mailbox's second post (the tile scan's;
+// `first_post` tells whether its first one arrived), else the pinned copy + stream synchronisation.  A mailbox whose post
+// did not arrive is marked failed: this thread stays with the copy from then on.
+int read_counters(const FwdCtx& x, const frg::Mailbox* mail, uint32_t mail_seq, bool first_post, frg::Counters* c)
+{
+    if (mail) {
+        if (first_post && mailbox_wait(&mail->seq_c, mail_seq, x.stream)) { *c = mail->c; return FRG_OK; }
+        g_mail.failed = true, g_mail.host = nullptr;    // (the pinned block is left to the process)
+    }
+    frg::Counters* host = pinned_counters();
+    if (!host) return fail(FRG_EHIP, "hipHostMalloc failed");
+    FRG_HIP(hipMemcpyAsync(host, x.img.counters, sizeof(frg::Counters), hipMemcpyDeviceToHost, x.stream));
+    FRG_HIP(hipStreamSynchronize(x.stream));
+    *c = *host;
+    return FRG_OK;
+}
+
+// small frames (at most 2^20 instances: C2 has 350 000 in 2 500 lists of 140): the lists of up to 512 entries are sorted by the
+// forward blend's own workgroups (blend_impl.h FUSED) -- one launch and the point_list round trip less in a step that is a
+// chain of short launches; the longest-first tile order (class lists) is what the fused form walks
+bool fused_small_sort(int R, int option, int fwd_order, int probe)
+{
+    return option != 0 && R > 0 && R <= (1 << 20) && fwd_order != 0 && !(probe & 1);
+}
+
+// A frame that does not fill the GPU (fewer than 1280 instances per tile of the image on average) and whose longest list
+// is several times its mean list -- the limb of a shell seen from outside (C4: 792 per tile, 6 267 against a mean of
+// 1 366 over the active tiles) -- walks eight entries per trip: its launch is stall-bound inside the waves of its long
+// tiles (0.240 -> 0.222 ms).  A full frame is bound by instruction issue and keeps four, uniform (C3: 0.203 -> 0.243 with
+// eight) or clustered (the skew scene, 2 670 per tile: 0.186 -> 0.218).  Same bits either way.  (option: "fwd_unroll8")
+bool eight_entries_per_trip(const frg::Counters& c, int R, int T, int option)
+{
+    if (R <= 0 || option == 0) return false;
+    uint32_t active = 0;
+    for (int k = 0; k < FRG_SORT_CLASSES; k++) active += c.class_count[k];
+    return option == 2 || ((double)(int)c.max_tile_count >= 3.5 * (double)R / (double)(active ? active : 1u) && (double)R < 1280.0 * (double)T);
+}
+
+// instance_capacity == 0: the reference's flow, one blocking read of the counters between scan and scatter.  The scan
+// workgroups post the counters into this thread's pinned mailbox (frg_common.h) and the host polls it, instead of a copy
+// kernel + stream synchronisation behind the scan.  First post: the instance count (by the chunk scan, ~40 us before the
+// scan stage ends at C3) -- the scatter goes out on it.  Second post: the tile scan's counters (the sort's grids).
+int forward_blocking(FwdCtx& x)
+{
+    const frg_forward_args& a = x.a;
+    const int P = a.P, debug = x.debug, T = x.T;
+    hipStream_t stream = x.stream;
+    const frg::ImageState& img = x.img;
+    FRG_TRY(clear_image_state(x));
+    FRG_TRY(stage_preprocess(x));
+    frg::Mailbox* mail = (!debug && g_use_mailbox.load(std::memory_order_relaxed)) ? g_mail.get() : nullptr;
+    uint32_t mail_seq = 0;
+    if (mail) { if (++g_mail.seq == 0) g_mail.seq = 1; mail_seq = g_mail.seq; }
+    FRG_TRY(stage_scan(x, mail, mail_seq));
+
+    // the single host synchronisation of the op (rasterizer_impl.cu:280-281)
+    frg::BinningState b;
+    bool early = false;
+    const bool first_post = mail && mailbox_wait(&mail->seq_r, mail_seq, stream);
+    if (first_post) {
+        const uint32_t r = mail->num_rendered;
+        if (r > 0x7fffffffu) return fail(FRG_EINVAL, "num_rendered overflows int32");
+        if (r > 0) { FRG_TRY(scatter_early(x, (int)r, mail, mail_seq, &b)); early = true; }
+    }
+    frg::Counters c;
+    FRG_TRY(read_counters(x, mail, mail_seq, first_post, &c));
+    if (a.prefiltered && c.filtered)
+        return fail(FRG_EFILTER, "Point is filtered although prefiltered is set. This shouldn't happen!");
+    if (c.num_rendered > 0x7fffffffu) return fail(FRG_EINVAL, "num_rendered overflows int32");
+    const int R = (int)c.num_rendered, max_tile = (int)c.max_tile_count;
+    g_fwd_notes.update(x.geom_chunk, [&](FwdNote& n) { n.rendered = R; });      // (a deferred forward does not know)
+
+    if (!early) FRG_TRY(x.alloc_binning(R, max_tile, &b));
+    const bool forked_plan = early && g_mail.long_lists;
+    if (mail) g_mail.long_lists = c.class_count[4] > 0;
+    const bool fused_small = fused_small_sort(R, g_fused_small.load(), frg::g_fwd_order.load(), g_probe.load());
+    const bool probe_fwd = (g_probe.load() & 1) && R > 0 && !x.md.exact && g_probe_side.ensure();
+    if (R > 0) {
+        FRG_STAGE(frg::launch_sort_plan(T, c.class_count, img.counters->class_count, img.class_tiles, img.ranges, b.big_plan, (uint32_t)R, stream, forked_plan ? 2 : 0), "sort plan");
+        if (!early) {
+            { StageScope sc_(ST_SCATTER, stream); FRG_STAGE(frg::launch_scatter(P, x.vp, x.radii, x.g, img, b, stream, g_ablate.load()), "scatter"); }
+            FRG_TRY(x.sh.fork(3, x));
+        }
+        if (probe_fwd) {
+            FRG_HIP(g_probe_side.fork_from(stream));
+            FRG_HIP(frg::launch_blend_fwd_fast(x.vp, x.g, img, b, a.background, a.out_color, g_probe_side.stream));
+            FRG_HIP(hipEventRecord(g_probe_side.join, g_probe_side.stream));
+        }
+        { StageScope sc_(ST_SORT, stream); FRG_STAGE(frg::launch_tile_sort(T, c.class_count, nullptr, img.counters->class_count, img.class_tiles, img.ranges, b.pairs, b.pairs_tmp, b.big_hist, b.big_plan, (uint32_t)R, max_tile, x.index_bits, b.point_list, stream, fused_small), "sort"); }
+        if (probe_fwd) { FRG_HIP(hipStreamWaitEvent(stream, g_probe_side.join, 0)); return R; }
+    } else {
+        // point_offsets must still be defined for backward
+        FRG_STAGE(frg::launch_scatter(P, x.vp, x.radii, x.g, img, b, stream), "scatter");
+        FRG_TRY(x.sh.fork(3, x));
+    }
+    FRG_TRY(x.sh.join(stream));
+    StageScope sc_(ST_BLEND_FWD, stream);
+    FRG_STAGE(x.blend(b, x.md.fwd_only != 0, fused_small, eight_entries_per_trip(c, R, T, g_fwd_unroll8.load())), "blend");
+    return R;
+}
+
+// Validates, asks the caller for the geometry and image chunks, then runs one of the two flows.  -> num_rendered
+// (deferred: the capacity) or a negative error code.
+int forward_impl(const frg_forward_args& a)
+{
+    FRG_TRY(validate_forward(a));
+    hipStream_t stream = (hipStream_t)a.hip_stream;
+    if (a.P == 0) {  // rasterize_points.cu:68,81: zero image, background not applied
+        FRG_HIP(hipMemsetAsync(a.out_color, 0, (size_t)3 * a.width * a.height * sizeof(float), stream));
+        return 0;
+    }
+    FwdCtx x{a};
+    x.md = default_modes();
+    x.md.exact = FwdModes::pick(a.exact_blend, 1, x.md.exact);
+    x.md.tight = FwdModes::pick(a.tight_binning, 1, x.md.tight);
+    x.md.async_sh = FwdModes::pick(a.async_sh, 3, x.md.async_sh);
+    x.md.fwd_only = a.forward_only;
+    x.debug = a.instance_capacity > 0 ? 0 : a.debug;
+    x.seg_forced = g_bwd_seg_log.load();
+    x.stream = stream;
+    x.vp = make_view(a.D, a.M, a.width, a.height, a.tan_fovx, a.tan_fovy, a.scale_modifier, x.md.tight);
+    // Will this view see only a part of the model?  With an occlusion mask: yes.  Otherwise: what the previous forward of
+    // this thread saw (posted by its scatter) -- the SH pass then streams the rows of the visible Gaussians only.
+    x.vp.sparse_sh = g_sparse_sh.load(std::memory_order_relaxed) && (a.keep_mask != nullptr || g_mail.sparse_view(a.P));
+    x.vp.sh_no_dir = (g_sh_no_dir.load(std::memory_order_relaxed) || x.md.fwd_only) ? 1 : 0;
+    x.T = x.vp.gx * x.vp.gy;
+    x.index_bits = 1;
+    while (x.index_bits < 32 && (1u << x.index_bits) < (uint32_t)a.P) x.index_bits++;
+
+    x.geom_chunk = a.geometry_alloc(a.user, frg_geometry_bytes(a.P));
+    x.img_chunk = a.image_alloc(a.user, frg_image_bytes(a.width, a.height));
+    if (!x.geom_chunk || !x.img_chunk) return fail(FRG_EALLOC, "allocation callback returned null");
+    g_fwd_notes.begin(x.geom_chunk, x.md.exact, x.md.fwd_only != 0);
+    x.g = frg::GeomState::carve(x.geom_chunk, a.P);
+    x.img = frg::ImageState::carve(x.img_chunk, a.width, a.height, g_global_bins.load() != 0);
+    x.radii = a.radii ? a.radii : x.g.internal_radii;   // rasterizer_impl.cu:228-231
+    x.in = frg::FwdInputs{a.means3D, a.scales, a.rotations, a.opacities, a.shs, a.cov3D_precomp, a.colors_precomp, a.viewmatrix, a.projmatrix, a.cam_pos};
+    x.in.keep_mask = a.keep_mask;
+    x.in.raw = raw_inputs_of(a);
+    x.sh.arm((a.shs != nullptr && !a.shell_logits) ? x.md.async_sh : 0);
+    return a.instance_capacity > 0 ? forward_deferred(x) : forward_blocking(x);
+}
+
+// the positional parameters of frg_forward / frg_forward_deferred are the struct's fields up to radii, in its order, and
+// hip_stream; debug and the later fields stay 0 / NULL: absent
+frg_forward_args positional_forward_args(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc, frg_alloc_fn image_alloc, void* user,
+                                         int P, int D, int M, const float* background, int width, int height,
+                                         const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
+                                         const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                         const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                                         float tan_fovx, float tan_fovy, int prefiltered, float* out_color, int* radii, void* hip_stream)
+{
+    return frg_forward_args{sizeof(frg_forward_args), geometry_alloc, binning_alloc, image_alloc, user, P, D, M, background,
+                            width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                            cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
+                            radii, /* debug */ 0, hip_stream};
+}
+
+// ---- backward -----------------------------------------------------------------
+// The argument checks of a backward up to its workspace, in the order their messages are promised (those of the phase
+// and the range follow the forward's stamp, in backward_impl).  An empty model (P == 0) needs nothing beyond sizes.
+int validate_backward(const frg_backward_args& a)
+{
+    if (a.exact_blend < 0 || a.exact_blend > 2 || a.shell_bary_mode < 0 || a.shell_bary_mode > 1)
+        return fail(FRG_EINVAL, "frg_backward_args: mode out of range (exact_blend %d, shell_bary_mode %d)", a.exact_blend, a.shell_bary_mode);
+    if (a.P < 0 || a.R < 0 || a.width <= 0 || a.height <= 0) return fail(FRG_EINVAL, "bad sizes");
+    if (a.P == 0) return FRG_OK;
+    if (!a.geom_buffer || !a.binning_buffer || !a.image_buffer || !a.dL_dpix || !a.background || !a.viewmatrix || !a.projmatrix || !a.campos)
+        return fail(FRG_EINVAL, "null required pointer");
+    if ((a.means3D == nullptr) == (a.shell_logits == nullptr)) return fail(FRG_EINVAL, "provide exactly one of means3D / shell_logits");
+    if (a.shell_logits && (!a.shell_cell_verts || !a.shell_cells || !a.dL_dshell_logits))
+        return fail(FRG_EINVAL, "shell_logits needs shell_cell_verts, shell_cells and dL_dshell_logits");
+    if (!a.dL_dmean2D || !a.dL_dopacity || !a.dL_dmean3D) return fail(FRG_EINVAL, "null gradient output");
+    // intermediates of the chain may be left out when the caller has no use for them: dL_dcolor when the SH rows are
+    // written (it is then only the factor of dL_dsh), dL_dcov3D when the covariance comes from scales / rotations
+    if (!a.dL_dcolor && !(a.shs && a.dL_dsh)) return fail(FRG_EINVAL, "dL_dcolor may only be NULL when shs and dL_dsh are given");
+    if (!a.dL_dcov3D && a.cov3D_precomp) return fail(FRG_EINVAL, "dL_dcov3D may only be NULL without cov3D_precomp");
+    if ((a.raw_scales == nullptr) != (a.raw_rotations == nullptr)) return fail(FRG_EINVAL, "raw_scales and raw_rotations come together");
+    if (((a.scales && (!a.dL_dscale || !a.dL_drot || !a.rotations))) || (a.raw_scales && (!a.dL_dscale || !a.dL_drot)))
+        return fail(FRG_EINVAL, "null gradient output for a provided input");
+    // R sizes the slots and the backward blend's item list: fewer than the forward rendered would overrun them.  (More is
+    // fine -- a deferred forward's capacity: where the forward's checkpoints lie in the binning chunk is taken from what the
+    // forward stamped, Counters::carved_R, not from R.)
+    if (a.workspace_bytes < frg_backward_workspace_bytes(a.P, a.R) || !a.workspace)
+        return fail(FRG_EALLOC, "workspace too small: need %zu bytes", frg_backward_workspace_bytes(a.P, a.R));
+    return FRG_OK;
+}
+
+// The arithmetic of this backward's blend pass (the backward recomputes its forward's alpha, T and contributor tests: the
+// same arithmetic keeps them consistent) and whether that forward kept anything for a backward were stamped into the
+// image chunk by the forward's blend kernel (Counters::fwd_flags): they travel with the buffers.  The host's notes are
+// keyed by ADDRESS -- a buffer copied to an address some earlier forward used would inherit that forward's note -- so
+// they decide nothing a stamp can contradict:
+//   * arithmetic: what the caller states (frg_backward_args::exact_blend; the Python layer carries it in its autograd
+//     ctx), else BOTH instantiations are launched and each leaves at once unless the stamp names it (*exact = -1);
+//   * forward_only: a note that says "an ordinary forward" lets the call through (a forward_only stamp then still leaves
+//     the kernels without work); anything else -- no note, or a note that says forward_only -- is settled by reading the
+//     stamp back, one blocking copy of the forward's counters, which also tells the arithmetic.
+//   * R: a note that says the forward rendered MORE instances than this call's R (slots and item lists would overrun) is
+//     checked against the stamped count the same way before the call is refused.
+// -> *exact: 1 | 0 as stated or stamped, -1 "as stamped, on the device"
+int settle_forward_stamp(const frg_backward_args& a, const std::optional<FwdNote>& note, int* exact)
+{
+    *exact = a.exact_blend == 0 ? -1 : FwdModes::pick(a.exact_blend, 1, 0);
+    const bool ask_the_stamp = !note || note->fwd_only || (note->rendered >= 0 && a.R < note->rendered);
+    if (!ask_the_stamp || a.phase == 2) return FRG_OK;
+    hipStream_t stream = (hipStream_t)a.hip_stream;
+    frg::Counters* host = pinned_counters();
+    if (!host) return fail(FRG_EHIP, "hipHostMalloc failed");
+    const frg::ImageState img0 = frg::ImageState::carve(a.image_buffer, a.width, a.height, false);
+    FRG_HIP(hipMemcpyAsync(host, img0.counters, sizeof(frg::Counters), hipMemcpyDeviceToHost, stream));
+    FRG_HIP(hipStreamSynchronize(stream));
+    const uint32_t flags = host->fwd_flags;
+    if (!(flags & FRG_FWD_STAMPED))
+        return fail(FRG_EINVAL, "the image buffer carries no forward's stamp: these are not the buffers of a completed frg_forward");
+    if (flags & FRG_FWD_ONLY)
+        return fail(FRG_EINVAL, "the forward that filled these buffers was called with forward_only = 1: it kept nothing for a backward");
+    if ((uint32_t)a.R < host->num_rendered)
+        return fail(FRG_EINVAL, "R = %d, but the forward that filled this geometry buffer rendered %u instances", a.R, host->num_rendered);
+    if (*exact < 0) *exact = (flags & FRG_FWD_EXACT) ? 1 : 0;
+    return FRG_OK;
+}
+
+// Where the two forms of the per-Gaussian backward go.  The 16-wave form for the Gaussians that own thousands of slots
+// runs beside the plain kernel (usually its workgroups find an empty list and leave); the forward's scatter posted how
+// many waves of Gaussians need it (Mailbox::heavy): none, usually -- the launch is then skipped.
+//   Known to exist: the few 16-wave workgroups go on the CALLER's stream and start at once on an empty GPU, the
+// plain kernel follows on the side stream a cross-queue hop later and fills the rest -- behind the plain kernel's
+// 47 k waves the 1024-thread workgroups waited for a whole free CU and ran mostly after it (clustered scene:
+// 0.41 -> 0.33 ms).  Unknown (no post): the 16-wave form on the high-priority side stream (g_bwd_side).
+struct PbwStreams {
+    hipStream_t heavy, plain;
+    bool side;           // one of the two is g_bwd_side's: fork before, join behind
+    bool skip_heavy;
+};
+PbwStreams pick_pbw_streams(hipStream_t stream, int debug, const std::optional<FwdNote>& note)
+{
+    const int heavy = g_assume_no_heavy.load(std::memory_order_relaxed) ? 0 : debug || !note ? -1 : note->heavy_waves_posted();
+    const bool skip_heavy = heavy == 0;
+    const bool side = !skip_heavy && !debug && g_bwd_side.ensure();
+    const bool heavy_first = side && heavy > 0 && g_bwd_heavy_first.load(std::memory_order_relaxed);
+    hipStream_t other = side ? g_bwd_side.stream : stream;
+    return PbwStreams{heavy_first ? stream : other, heavy_first ? other : stream, side, skip_heavy};
+}
+
+int backward_impl(const frg_backward_args& a)
+{
+    FRG_TRY(validate_backward(a));
+    if (a.P == 0) return FRG_OK;
+    const int P = a.P, R = a.R, debug = a.debug, phase = a.phase;
+    hipStream_t stream = (hipStream_t)a.hip_stream;
+    const std::optional<FwdNote> note = g_fwd_notes.find(a.geom_buffer);
+    int exact;
+    FRG_TRY(settle_forward_stamp(a, note, &exact));
+
+    // Nothing here depends on the process-wide binning options: every field of the three chunks that the
+    // backward reads is carved from (P, W, H, R) alone (the option-dependent matrices of the binning stage
+    // come last in the image chunk), and the kernels take the forward's binning mode from the counters it
+    // stamped.  "exact_blend" only selects the arithmetic of this backward's own blend pass.
+    const frg::ViewParams vp = make_view(a.D, a.M, a.width, a.height, a.tan_fovx, a.tan_fovy, a.scale_modifier, 0);
+    const frg::GeomState g = frg::GeomState::carve(a.geom_buffer, P);
+    const frg::ImageState img = frg::ImageState::carve(a.image_buffer, a.width, a.height, false);
+    const frg::BinningState b = frg::BinningState::carve(a.binning_buffer, R, 0);
+    const frg::BwdWorkspace ws = frg::BwdWorkspace::carve(a.workspace, P, R);
+    unsigned long long* const live_masks = phase == 1 ? ws.live_masks : nullptr;
+    if (phase < 0 || phase > 2) return fail(FRG_EINVAL, "frg_backward_args: phase %d (0 whole | 1 blend + slot sums | 2 the rest)", phase);
+    const int* const radii = a.radii ? a.radii : g.internal_radii;   // rasterizer_impl.cu:375-377
+
+    frg::FwdInputs in{a.means3D, a.scales, a.rotations, nullptr, a.shs, a.cov3D_precomp, a.colors_precomp, a.viewmatrix, a.projmatrix, a.campos};
+    in.raw = raw_inputs_of(a);
+    frg::BwdOutputs out{a.dL_dmean2D, a.dL_dconic, a.dL_dopacity, a.dL_dcolor, a.dL_dmean3D, a.dL_dcov3D, a.dL_dsh, a.dL_dscale, a.dL_drot};
+    out.dL_dshell_logits = a.dL_dshell_logits;
+    out.dL_dshell_verts = a.dL_dshell_cell_verts;
+    out.row_live = a.row_live;
+    const int pbw_flags = phase == 1 ? FRG_PBW_SUMS_ONLY : phase == 2 ? FRG_PBW_FROM_SUMS : 0;
+    // the per-Gaussian backward: each call site states its flags, its form (heavy_only), its stream and, in phase 1, what it leaves
+    auto preprocess_bwd = [&](int flags, bool heavy_only, hipStream_t s, unsigned long long* masks = nullptr, float* dirs = nullptr,
+                              int range_first = 0, int range_count = 0) {
+        return frg::launch_preprocess_bwd(P, vp, in, radii, g, img, ws.slots, out, g_ablate.load(), flags, heavy_only, s, ws.sums, masks, dirs,
+                                          range_first, range_count);
+    };
+    if (phase == 2) {     // the sums are in the workspace: one launch, no slot reduction, hence no 16-wave form either
+        if (!g_phase_notes.consume(a.workspace, a.geom_buffer, a.image_buffer, P, R))
+            return fail(FRG_EINVAL, "backward phase 2 without a matching phase 1 on this workspace (same P, R, geometry and image buffers)");
+        StageScope sc_(ST_PREPROCESS_BWD, stream);
+        FRG_STAGE(preprocess_bwd(pbw_flags | FRG_PBW_NO_HEAVY_LAUNCH, false, stream), "preprocess_bwd (phase 2)");
+        return FRG_OK;
+    }
+    if (phase == 1) g_phase_notes.record(a.workspace, a.geom_buffer, a.image_buffer, P, R);
+    const bool ranged = a.range_count > 0;
+    if (ranged) {
+        if (phase != 1) return fail(FRG_EINVAL, "frg_backward_args: a range is offered with phase 1 only (phase %d)", phase);
+        if (a.range_first < 0 || a.range_first % 256 != 0 || (long long)a.range_first + a.range_count > P)
+            return fail(FRG_EINVAL, "frg_backward_args: range [%d, +%d) of %d Gaussians (range_first: a multiple of 256)", a.range_first, a.range_count, P);
+    }
+    const bool probe_bwd = (g_probe.load() & 2) && g_probe_side.ensure();
+    if (probe_bwd) {   // timing experiment: the per-Gaussian backward beside the blend (it reads the previous frame's slots)
+        FRG_HIP(g_probe_side.fork_from(stream));
+        FRG_HIP(preprocess_bwd(pbw_flags, false, g_probe_side.stream));
+        FRG_HIP(preprocess_bwd(pbw_flags, true, g_probe_side.stream));
+        FRG_HIP(hipEventRecord(g_probe_side.join, g_probe_side.stream));
+    }
+    if (!ranged || a.range_first == 0) {
+        StageScope sc_(ST_BLEND_BWD, stream);
+        if (exact != 0)
+            FRG_STAGE(frg::launch_blend_bwd_exact(vp, g, img, b, a.background, a.dL_dpix, ws.slots, (uint32_t)R, g_bwd_batch.load(), stream, exact < 0), "blend_bwd");
+        if (exact <= 0)
+            FRG_STAGE(frg::launch_blend_bwd_fast(vp, g, img, b, a.background, a.dL_dpix, ws.slots, (uint32_t)R, g_bwd_batch.load(), stream, exact < 0), "blend_bwd");
+    }
+    if (probe_bwd) { FRG_HIP(hipStreamWaitEvent(stream, g_probe_side.join, 0)); return FRG_OK; }
+    StageScope sc_(ST_PREPROCESS_BWD, stream);
+    if (ranged) {      // phase 1 in pieces: the plain kernel over this range, whatever its waves own (no 16-wave side launch)
+        FRG_STAGE(preprocess_bwd(pbw_flags | FRG_PBW_NO_HEAVY_LAUNCH, false, stream, live_masks, ws.dir_terms, a.range_first, a.range_count), "preprocess_bwd (phase 1, range)");
+        return FRG_OK;
+    }
+    const PbwStreams to = pick_pbw_streams(stream, debug, note);
+    if (to.side) FRG_HIP(g_bwd_side.fork_from(stream));
+    if (!to.skip_heavy)
+        FRG_STAGE(preprocess_bwd(pbw_flags, true, to.heavy, live_masks, ws.dir_terms), "preprocess_bwd (long runs)");
+    FRG_STAGE(preprocess_bwd(pbw_flags | (to.skip_heavy ? FRG_PBW_NO_HEAVY_LAUNCH : 0), false, to.plain, live_masks, ws.dir_terms), "preprocess_bwd");
+    if (to.side) { FRG_HIP(hipEventRecord(g_bwd_side.join, g_bwd_side.stream)); FRG_HIP(hipStreamWaitEvent(stream, g_bwd_side.join, 0)); }
+    return FRG_OK;
 }
 
 }  // namespace
@@ -470,6 +980,13 @@ int frg_set_option(const char* name, int value)
     }
     if (o->value == &g_exact_blend) (void)exact_blend();      // the previous value is the resolved one
     return o->value->exchange(o->stored(value));
+}
+
+int frg_get_option(const char* name)
+{
+    const Option* o = find_option(name);
+    if (!o || o->experiment) return fail(FRG_EINVAL, "unknown option '%s'", name ? name : "(null)");
+    return o->value == &g_exact_blend ? exact_blend() : o->value->load();
 }
 
 int frg_stage_times(float* ms, int n)
@@ -496,32 +1013,10 @@ int frg_stage_times(float* ms, int n)
     return ST_COUNT;
 }
 
-int frg_get_option(const char* name)
-{
-    const Option* o = find_option(name);
-    if (!o || o->experiment) return fail(FRG_EINVAL, "unknown option '%s'", name ? name : "(null)");
-    return o->value == &g_exact_blend ? exact_blend() : o->value->load();
-}
-
 size_t frg_geometry_bytes(int P) { return frg::GeomState::carve(nullptr, P).bytes; }
 size_t frg_image_bytes(int width, int height) { return frg::ImageState::carve(nullptr, width, height, g_global_bins.load() != 0).bytes; }
 size_t frg_binning_bytes(int R, int max_tile_count) { return frg::BinningState::carve(nullptr, R, max_tile_count, g_bwd_seg_log.load()).bytes; }
-// slots (36 B per instance) ...
-static size_t slots_bytes(int R) { return frg::align_up((size_t)(R > 0 ? R : 1) * FRG_SLOT_STRIDE * sizeof(float), 256); }
-// ... + the nine per-Gaussian sums a two-call backward (frg_backward_args::phase) keeps between its calls.  (The backward
-// blend's work items are listed by the forward, in its own chunks: frg_common.h, BinningState::bwd_full, ImageState::bwd_last.)
-static size_t sums_bytes(int P) { return frg::align_up((size_t)(P > 0 ? P : 1) * FRG_SLOT_FLOATS * sizeof(float), 256); }
-// ... + one bit per Gaussian, "its sums are not all zero", left by phase 1 for the slot-sum exchange (whole 256-Gaussian workgroups)
-static size_t live_mask_words(int P) { return (size_t)(P > 0 ? P : 1) / 64 + 8; }
-// ... + the pack's scratch: one row count per group of 256 such words
-static size_t live_mask_bytes(int P) { return frg::align_up(live_mask_words(P) * 8, 256); }
-// ... + the three view-direction terms per Gaussian that phase 1 leaves for the slot-sum packets
-static size_t dir_terms_bytes(int P) { return frg::align_up((size_t)(P > 0 ? P : 1) * 3 * sizeof(float), 256); }
-static size_t pack_scratch_bytes(int P) { return frg::align_up((live_mask_words(P) / 256 + 8) * 4, 256); }
-size_t frg_backward_workspace_bytes(int P, int R)
-{
-    return slots_bytes(R) + sums_bytes(P) + live_mask_bytes(P) + pack_scratch_bytes(P) + dir_terms_bytes(P);
-}
+size_t frg_backward_workspace_bytes(int P, int R) { return frg::BwdWorkspace::carve(nullptr, P, R).bytes; }
 
 int frg_geometry_layout_n(int P, long long* out, int n)
 {
@@ -556,246 +1051,6 @@ int frg_mark_visible(int P, const float* means3D, const float* viewmatrix, const
     return FRG_OK;
 }
 
-// capacity == 0: the reference's flow, one blocking read-back of the counters between scan and
-// scatter.  capacity > 0: no host synchronisation at all -- the binning buffer is sized for
-// `capacity` instances up front, launches that depend on the counters use device-side values,
-// and the counters travel to a pinned slot that frg_forward_finish() inspects later.
-static int forward_impl(const frg_forward_args& a)
-{
-    if (a.instance_capacity < 0) return fail(FRG_EINVAL, "instance_capacity < 0");
-    if (a.forward_only < 0 || a.forward_only > 1) return fail(FRG_EINVAL, "frg_forward_args: forward_only must be 0 or 1");
-    if (a.forward_only && a.instance_capacity > 0)
-        return fail(FRG_EINVAL, "frg_forward_args: forward_only with deferred counters (instance_capacity > 0) is not offered");
-    if (a.exact_blend < 0 || a.exact_blend > 2 || a.tight_binning < 0 || a.tight_binning > 2 || a.async_sh < 0 ||
-        a.async_sh > 4 || a.shell_bary_mode < 0 || a.shell_bary_mode > 1)
-        return fail(FRG_EINVAL, "frg_forward_args: mode out of range (exact_blend %d, tight_binning %d, async_sh %d, shell_bary_mode %d)",
-                    a.exact_blend, a.tight_binning, a.async_sh, a.shell_bary_mode);
-    const int P = a.P, width = a.width, height = a.height, prefiltered = a.prefiltered, capacity = a.instance_capacity;
-    const int debug = capacity > 0 ? 0 : a.debug;     // (deferred counters: no synchronisation, the stage-by-stage one included)
-    const float* const background = a.background;
-    float* const out_color = a.out_color;
-    hipStream_t stream = (hipStream_t)a.hip_stream;
-    FwdModes md = default_modes();
-    md.exact = FwdModes::pick(a.exact_blend, 1, md.exact);
-    md.tight = FwdModes::pick(a.tight_binning, 1, md.tight);
-    md.async_sh = FwdModes::pick(a.async_sh, 3, md.async_sh);
-    md.fwd_only = a.forward_only;
-    const int exact = md.exact;
-    const int seg_forced = g_bwd_seg_log.load();      // (read once: the size asked of the callback and the carve must agree)
-    // the binning chunk of R_ instances whose longest tile list has `longest` entries, from the caller's callback
-    auto alloc_binning = [&a, seg_forced](int R_, int longest, frg::BinningState* b_) -> int {
-        char* bin_chunk = a.binning_alloc(a.user, frg::BinningState::carve(nullptr, R_, longest, seg_forced).bytes);
-        if (!bin_chunk) return fail(FRG_EALLOC, "binning allocation callback returned null");
-        *b_ = frg::BinningState::carve(bin_chunk, R_, longest, seg_forced);
-        return FRG_OK;
-    };
-    const auto launch_blend_fwd = exact ? frg::launch_blend_fwd_exact : frg::launch_blend_fwd_fast;
-    if (P < 0 || width <= 0 || height <= 0) return fail(FRG_EINVAL, "bad sizes P=%d W=%d H=%d", P, width, height);
-    if (!out_color) return fail(FRG_EINVAL, "out_color is null");
-    if (P == 0) {  // rasterize_points.cu:68,81: zero image, background not applied
-        FRG_HIP(hipMemsetAsync(out_color, 0, (size_t)3 * width * height * sizeof(float), stream));
-        return 0;
-    }
-    frg::RawInputs rw;
-    rw.raw_opacity = a.raw_opacities; rw.raw_scale = a.raw_scales; rw.raw_rot = a.raw_rotations;
-    rw.shell_logits = a.shell_logits; rw.shell_verts = a.shell_cell_verts; rw.shell_cells = a.shell_cells;
-    rw.bary_mode = a.shell_bary_mode;
-    if (!a.viewmatrix || !a.projmatrix || !a.cam_pos || !background) return fail(FRG_EINVAL, "null required pointer");
-    if ((a.means3D == nullptr) == (rw.shell_logits == nullptr))
-        return fail(FRG_EINVAL, "provide exactly one of means3D / shell_logits");
-    if (rw.shell_logits && (!rw.shell_verts || !rw.shell_cells))
-        return fail(FRG_EINVAL, "shell_logits needs shell_cell_verts and shell_cells");
-    if ((a.opacities == nullptr) == (rw.raw_opacity == nullptr))
-        return fail(FRG_EINVAL, "provide exactly one of opacities / raw_opacities");
-    if ((a.shs == nullptr) == (a.colors_precomp == nullptr))
-        return fail(FRG_EINVAL, "provide exactly one of shs / colors_precomp");
-    if ((rw.raw_scale == nullptr) != (rw.raw_rot == nullptr))
-        return fail(FRG_EINVAL, "raw_scales and raw_rotations come together");
-    const bool have_sr = (a.scales && a.rotations) || rw.raw_scale;
-    if ((a.scales || a.rotations) && rw.raw_scale) return fail(FRG_EINVAL, "provide (scales, rotations) or their raw forms, not both");
-    if (((a.scales == nullptr) != (a.rotations == nullptr)) || have_sr == (a.cov3D_precomp != nullptr))
-        return fail(FRG_EINVAL, "provide exactly one of (scales, rotations) / cov3D_precomp");
-    if (a.shs && (a.D < 0 || a.D > 3 || a.M < (a.D + 1) * (a.D + 1)))
-        return fail(FRG_EINVAL, "SH degree %d needs %d coefficients, got M=%d", a.D, (a.D + 1) * (a.D + 1), a.M);
-    if (!a.geometry_alloc || !a.binning_alloc || !a.image_alloc) return fail(FRG_EINVAL, "null allocation callback");
-
-    frg::ViewParams vp = make_view(P, a.D, a.M, width, height, a.tan_fovx, a.tan_fovy, a.scale_modifier, md.tight);
-    // Will this view see only a part of the model?  With an occlusion mask: yes.  Otherwise: what the previous forward of
-    // this thread saw (posted by its scatter) -- the SH pass then streams the rows of the visible Gaussians only.
-    vp.sparse_sh = g_sparse_sh.load(std::memory_order_relaxed) && (a.keep_mask != nullptr || g_mail.sparse_view(P));
-    vp.sh_no_dir = (g_sh_no_dir.load(std::memory_order_relaxed) || md.fwd_only) ? 1 : 0;
-    const int T = vp.gx * vp.gy;
-
-    char* geom_chunk = a.geometry_alloc(a.user, frg_geometry_bytes(P));
-    char* img_chunk = a.image_alloc(a.user, frg_image_bytes(width, height));
-    if (!geom_chunk || !img_chunk) return fail(FRG_EALLOC, "allocation callback returned null");
-    g_fwd_notes.begin(geom_chunk, exact, md.fwd_only != 0);
-    const frg::GeomState g = frg::GeomState::carve(geom_chunk, P);
-    const frg::ImageState img = frg::ImageState::carve(img_chunk, width, height, g_global_bins.load() != 0);
-    int* const radii = a.radii ? a.radii : g.internal_radii;   // rasterizer_impl.cu:228-231
-
-    PendingCounters* pend = nullptr;
-    if (capacity > 0) {
-        bool reused = false;
-        pend = g_pending.acquire(img_chunk, &reused);
-        if (!pend) return fail(FRG_EHIP, "pinned counter slot / event creation failed");
-        // the previous deferred forward on this image buffer reads its counters back on a side stream:
-        // that copy must have happened before the counters are cleared again
-        if (reused) FRG_HIP(hipStreamWaitEvent(stream, pend->ev, 0));
-    }
-    // LDS-bins paths: nothing of the image chunk needs clearing in front of the forward -- colsum_kernel zeroes the
-    // scatter cursors and the blend's depth marks on its way, every counter is written unconditionally; only the flag
-    // of the prefiltered assertion is set-only.  Global bins (more tiles than the LDS holds): the per-tile counts are
-    // accumulated with atomics, the whole region is cleared.
-    if (!img.lds_bins || g_clear_image_state.load(std::memory_order_relaxed)) FRG_HIP(hipMemsetAsync(img_chunk + img.zero_begin, 0, img.zero_bytes, stream));
-    else if (prefiltered || capacity > 0) FRG_HIP(hipMemsetAsync(&img.counters->filtered, 0, sizeof(uint32_t), stream));   // (deferred: frg_forward_finish is told `prefiltered` again)
-
-    frg::FwdInputs in{a.means3D, a.scales, a.rotations, a.opacities, a.shs, a.cov3D_precomp, a.colors_precomp, a.viewmatrix, a.projmatrix, a.cam_pos};
-    in.keep_mask = a.keep_mask;
-    in.raw = rw;
-    // SH colours: nothing before the blend needs them, and the stages in between (scan, scatter, sort) leave the
-    // HBM nearly idle -- the colour kernel (the largest single stream of the forward, 192 B per visible Gaussian)
-    // runs beside them on a side stream; the blend joins it.
-    const int sh_mode = (a.shs != nullptr && !rw.shell_logits) ? md.async_sh : 0;   // 0 inside preprocess | side stream forked after: 1 preprocess, 2 scan, 3 scatter
-    const bool defer_sh = sh_mode != 0 && g_sh_side.ensure();
-    bool sh_forked = false;
-    // an error return between the fork and the join must not leave the side kernel running on the caller's inputs
-    struct ShJoin {
-        bool armed; hipStream_t side;
-        ~ShJoin() { if (armed) (void)hipStreamSynchronize(side); }
-    } sh_join{false, g_sh_side.stream};
-    auto fork_sh = [&](int at) -> int {
-        if (!defer_sh || sh_forked || (at < sh_mode && at < 3)) return FRG_OK;
-        sh_forked = true;
-        sh_join.armed = true;
-        FRG_HIP(g_sh_side.fork_from(stream));
-        {
-            StageScope sc_(ST_SH_COLOR, g_sh_side.stream);
-            FRG_HIP(frg::launch_sh_color(P, vp, in, radii, g, g_sh_side.stream));
-        }
-        FRG_HIP(hipEventRecord(g_sh_side.join, g_sh_side.stream));
-        if (debug) FRG_HIP(hipStreamSynchronize(g_sh_side.stream));
-        return FRG_OK;
-    };
-    { StageScope sc_(ST_PREPROCESS, stream); FRG_STAGE(frg::launch_preprocess_fwd(P, vp, in, radii, g, img, prefiltered, defer_sh, stream), "preprocess"); }
-    FRG_TRY(fork_sh(1));
-    // blocking form: the scan workgroups post the counters into this thread's pinned mailbox (frg_common.h) and the
-    // host polls it, instead of a copy kernel + stream synchronisation behind the scan
-    frg::Mailbox* mail = (capacity == 0 && !debug && g_use_mailbox.load(std::memory_order_relaxed)) ? g_mail.get() : nullptr;
-    uint32_t mail_seq = 0;
-    if (mail) { if (++g_mail.seq == 0) g_mail.seq = 1; mail_seq = g_mail.seq; }
-    { StageScope sc_(ST_SCAN, stream); FRG_STAGE(frg::launch_scan(P, vp, g, img, (uint32_t)capacity, stream, mail, mail_seq), "scan"); }
-    FRG_TRY(fork_sh(2));
-
-    int index_bits = 1;
-    while (index_bits < 32 && (1u << index_bits) < (uint32_t)P) index_bits++;
-    int R = capacity;
-    if (capacity > 0) {
-        // deferred counters: everything below is enqueued without knowing R on the host; the
-        // 48-byte read-back rides a side stream so that no later kernel queues behind it
-        FRG_HIP(hipEventRecord(pend->scanned, stream));
-        FRG_HIP(hipStreamWaitEvent(pend->copy_stream, pend->scanned, 0));
-        FRG_HIP(hipMemcpyAsync(pend->host, img.counters, sizeof(frg::Counters), hipMemcpyDeviceToHost, pend->copy_stream));
-        FRG_HIP(hipEventRecord(pend->ev, pend->copy_stream));
-        frg::BinningState b;
-        FRG_TRY(alloc_binning(capacity, FRG_SORT_LDS_CAP + 1, &b));
-        FRG_STAGE(frg::launch_sort_plan(T, nullptr, img.counters->class_count, img.class_tiles, img.ranges, b.big_plan, (uint32_t)capacity, stream), "sort plan");
-        { StageScope sc_(ST_SCATTER, stream); FRG_STAGE(frg::launch_scatter(P, vp, radii, g, img, b, stream, g_ablate.load()), "scatter"); }
-        FRG_TRY(fork_sh(3));
-        { StageScope sc_(ST_SORT, stream); FRG_STAGE(frg::launch_tile_sort(T, nullptr, g_pending.have_hint ? g_pending.last_class_count : nullptr, img.counters->class_count, img.class_tiles, img.ranges, b.pairs, b.pairs_tmp, b.big_hist, b.big_plan, (uint32_t)capacity, 0, index_bits, b.point_list, stream), "sort"); }
-        if (defer_sh) { FRG_HIP(hipStreamWaitEvent(stream, g_sh_side.join, 0)); sh_join.armed = false; }
-        StageScope sc_(ST_BLEND_FWD, stream);
-        FRG_STAGE(launch_blend_fwd(vp, g, img, b, background, out_color, stream, false, false, false), "blend");
-        return R;
-    }
-
-    // the single host synchronisation of the op (rasterizer_impl.cu:280-281)
-    frg::Counters c;
-    frg::BinningState b;
-    bool have_counters = false, early = false;
-    if (mail) {
-        // Stage 1: the instance count (posted by the chunk scan, ~40 us before the scan stage ends at C3).  The binning
-        // buffer is sized for every sort path -- the longest tile list is not known yet -- and the scatter is enqueued
-        // while the reorder still runs.  Stage 2: the tile scan's counters (the sort's grids).
-        if (mailbox_wait(&mail->seq_r, mail_seq, stream)) {
-            const uint32_t r = mail->num_rendered;
-            if (r > 0x7fffffffu) return fail(FRG_EINVAL, "num_rendered overflows int32");
-            if (r > 0) {
-                R = (int)r;
-                FRG_TRY(alloc_binning(R, FRG_SORT_LDS_CAP + 1, &b));
-                if (g_mail.long_lists)
-                    FRG_STAGE(frg::launch_sort_plan(T, nullptr, img.counters->class_count, img.class_tiles, img.ranges, b.big_plan, (uint32_t)R, stream, 1), "sort plan");
-                { StageScope sc_(ST_SCATTER, stream); FRG_STAGE(frg::launch_scatter(P, vp, radii, g, img, b, stream, g_ablate.load(), mail, mail_seq), "scatter"); }
-                FRG_TRY(fork_sh(3));
-                g_fwd_notes.update(geom_chunk, [&](FwdNote& n) { n.mail = mail; n.seq = mail_seq; });
-                g_mail.last_P = P; g_mail.last_seq = mail_seq;
-                early = true;
-            }
-            if (mailbox_wait(&mail->seq_c, mail_seq, stream)) { c = mail->c; have_counters = true; }
-        }
-        if (!have_counters) g_mail.failed = true, g_mail.host = nullptr;    // (the pinned block is left to the process)
-    }
-    if (!have_counters) {
-        frg::Counters* host = pinned_counters();
-        if (!host) return fail(FRG_EHIP, "hipHostMalloc failed");
-        FRG_HIP(hipMemcpyAsync(host, img.counters, sizeof(frg::Counters), hipMemcpyDeviceToHost, stream));
-        FRG_HIP(hipStreamSynchronize(stream));
-        c = *host;
-    }
-    if (prefiltered && c.filtered)
-        return fail(FRG_EFILTER, "Point is filtered although prefiltered is set. This shouldn't happen!");
-    if (c.num_rendered > 0x7fffffffu) return fail(FRG_EINVAL, "num_rendered overflows int32");
-    R = (int)c.num_rendered;
-    const int max_tile = (int)c.max_tile_count;
-    g_fwd_notes.update(geom_chunk, [&](FwdNote& n) { n.rendered = R; });      // (a deferred forward does not know)
-
-    if (!early) FRG_TRY(alloc_binning(R, max_tile, &b));
-    const bool forked_plan = early && g_mail.long_lists;
-    if (mail) g_mail.long_lists = c.class_count[4] > 0;
-
-    // small frames (at most 2^20 instances: C2 has 350 000 in 2 500 lists of 140): the lists of up to 512 entries are sorted by the
-    // forward blend's own workgroups (blend_impl.h FUSED) -- one launch and the point_list round trip less in a step that is a
-    // chain of short launches; the longest-first tile order (class lists) is what the fused form walks
-    const bool fused_small = g_fused_small.load() != 0 && R > 0 && R <= (1 << 20) && frg::g_fwd_order.load() != 0 && !(g_probe.load() & 1);
-    const bool probe_fwd = (g_probe.load() & 1) && R > 0 && !exact && g_probe_side.ensure();
-    if (R > 0) {
-        FRG_STAGE(frg::launch_sort_plan(T, c.class_count, img.counters->class_count, img.class_tiles, img.ranges, b.big_plan, (uint32_t)R, stream, forked_plan ? 2 : 0), "sort plan");
-        if (!early) {
-            { StageScope sc_(ST_SCATTER, stream); FRG_STAGE(frg::launch_scatter(P, vp, radii, g, img, b, stream, g_ablate.load()), "scatter"); }
-            FRG_TRY(fork_sh(3));
-        }
-        if (probe_fwd) {
-            FRG_HIP(g_probe_side.fork_from(stream));
-            FRG_HIP(frg::launch_blend_fwd_fast(vp, g, img, b, background, out_color, g_probe_side.stream));
-            FRG_HIP(hipEventRecord(g_probe_side.join, g_probe_side.stream));
-        }
-        { StageScope sc_(ST_SORT, stream); FRG_STAGE(frg::launch_tile_sort(T, c.class_count, nullptr, img.counters->class_count, img.class_tiles, img.ranges, b.pairs, b.pairs_tmp, b.big_hist, b.big_plan, (uint32_t)R, max_tile, index_bits, b.point_list, stream, fused_small), "sort"); }
-        if (probe_fwd) { FRG_HIP(hipStreamWaitEvent(stream, g_probe_side.join, 0)); return R; }
-    } else {
-        // point_offsets must still be defined for backward
-        FRG_STAGE(frg::launch_scatter(P, vp, radii, g, img, b, stream), "scatter");
-        FRG_TRY(fork_sh(3));
-    }
-    if (defer_sh) { FRG_HIP(hipStreamWaitEvent(stream, g_sh_side.join, 0)); sh_join.armed = false; }
-    {
-        StageScope sc_(ST_BLEND_FWD, stream);
-        // A frame that does not fill the GPU (fewer than 1280 instances per tile of the image on average) and whose longest list
-        // is several times its mean list -- the limb of a shell seen from outside (C4: 792 per tile, 6 267 against a mean of
-        // 1 366 over the active tiles) -- walks eight entries per trip: its launch is stall-bound inside the waves of its long
-        // tiles (0.240 -> 0.222 ms).  A full frame is bound by instruction issue and keeps four, uniform (C3: 0.203 -> 0.243 with
-        // eight) or clustered (the skew scene, 2 670 per tile: 0.186 -> 0.218).  Same bits either way.
-        bool long_lists = false;
-        if (R > 0 && g_fwd_unroll8.load() != 0) {
-            uint32_t active = 0;
-            for (int k = 0; k < FRG_SORT_CLASSES; k++) active += c.class_count[k];
-            long_lists = g_fwd_unroll8.load() == 2 ||
-                         ((double)max_tile >= 3.5 * (double)R / (double)(active ? active : 1u) && (double)R < 1280.0 * (double)T);
-        }
-        FRG_STAGE(launch_blend_fwd(vp, g, img, b, background, out_color, stream, md.fwd_only != 0, fused_small, long_lists), "blend");
-    }
-    return R;
-}
-
 int frg_forward(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc, frg_alloc_fn image_alloc, void* user,
                 int P, int D, int M, const float* background, int width, int height,
                 const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
@@ -804,11 +1059,11 @@ int frg_forward(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc, frg_all
                 float tan_fovx, float tan_fovy, int prefiltered,
                 float* out_color, int* radii, int debug, void* hip_stream)
 {
-    // (the parameters are the struct's fields up to hip_stream, in its order; the later fields stay 0 / NULL: absent)
-    return forward_impl(frg_forward_args{sizeof(frg_forward_args), geometry_alloc, binning_alloc, image_alloc, user, P, D, M, background,
-                                         width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                                         cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
-                                         radii, debug, hip_stream});
+    frg_forward_args a = positional_forward_args(geometry_alloc, binning_alloc, image_alloc, user, P, D, M, background, width, height, means3D, shs,
+                                                 colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
+                                                 projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, radii, hip_stream);
+    a.debug = debug;
+    return forward_impl(a);
 }
 
 int frg_forward_deferred(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc, frg_alloc_fn image_alloc, void* user,
@@ -820,10 +1075,11 @@ int frg_forward_deferred(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc
                          float* out_color, int* radii, int instance_capacity, void* hip_stream)
 {
     if (instance_capacity <= 0) return fail(FRG_EINVAL, "instance_capacity must be positive");
-    return forward_impl(frg_forward_args{sizeof(frg_forward_args), geometry_alloc, binning_alloc, image_alloc, user, P, D, M, background,
-                                         width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                                         cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
-                                         radii, /* debug */ 0, hip_stream, instance_capacity});
+    frg_forward_args a = positional_forward_args(geometry_alloc, binning_alloc, image_alloc, user, P, D, M, background, width, height, means3D, shs,
+                                                 colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
+                                                 projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, radii, hip_stream);
+    a.instance_capacity = instance_capacity;
+    return forward_impl(a);
 }
 
 int frg_forward_ex(const frg_forward_args* a)
@@ -858,158 +1114,6 @@ int frg_forward_finish(const char* image_buffer, int prefiltered, int* num_rende
     return FRG_OK;
 }
 
-}  // extern "C"
-
-static int backward_impl(const frg_backward_args& a)
-{
-    if (a.exact_blend < 0 || a.exact_blend > 2 || a.shell_bary_mode < 0 || a.shell_bary_mode > 1)
-        return fail(FRG_EINVAL, "frg_backward_args: mode out of range (exact_blend %d, shell_bary_mode %d)", a.exact_blend, a.shell_bary_mode);
-    const int P = a.P, R = a.R, width = a.width, height = a.height, debug = a.debug, phase = a.phase;
-    const float *const means3D = a.means3D, *const shs = a.shs, *const scales = a.scales, *const background = a.background, *const dL_dpix = a.dL_dpix;
-    char *const geom_buffer = a.geom_buffer, *const image_buffer = a.image_buffer, *const workspace = a.workspace;
-    hipStream_t stream = (hipStream_t)a.hip_stream;
-    frg::RawInputs rw;
-    rw.raw_opacity = a.raw_opacities; rw.raw_scale = a.raw_scales; rw.raw_rot = a.raw_rotations;
-    rw.shell_logits = a.shell_logits; rw.shell_verts = a.shell_cell_verts; rw.shell_cells = a.shell_cells;
-    rw.bary_mode = a.shell_bary_mode;
-    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(FRG_EINVAL, "bad sizes");
-    if (P == 0) return FRG_OK;
-    if (!geom_buffer || !a.binning_buffer || !image_buffer || !dL_dpix || !background || !a.viewmatrix || !a.projmatrix || !a.campos)
-        return fail(FRG_EINVAL, "null required pointer");
-    if ((means3D == nullptr) == (rw.shell_logits == nullptr)) return fail(FRG_EINVAL, "provide exactly one of means3D / shell_logits");
-    if (rw.shell_logits && (!rw.shell_verts || !rw.shell_cells || !a.dL_dshell_logits))
-        return fail(FRG_EINVAL, "shell_logits needs shell_cell_verts, shell_cells and dL_dshell_logits");
-    if (!a.dL_dmean2D || !a.dL_dopacity || !a.dL_dmean3D) return fail(FRG_EINVAL, "null gradient output");
-    // intermediates of the chain may be left out when the caller has no use for them: dL_dcolor when the SH rows are
-    // written (it is then only the factor of dL_dsh), dL_dcov3D when the covariance comes from scales / rotations
-    if (!a.dL_dcolor && !(shs && a.dL_dsh)) return fail(FRG_EINVAL, "dL_dcolor may only be NULL when shs and dL_dsh are given");
-    if (!a.dL_dcov3D && a.cov3D_precomp) return fail(FRG_EINVAL, "dL_dcov3D may only be NULL without cov3D_precomp");
-    if ((rw.raw_scale == nullptr) != (rw.raw_rot == nullptr)) return fail(FRG_EINVAL, "raw_scales and raw_rotations come together");
-    if (((scales && (!a.dL_dscale || !a.dL_drot || !a.rotations))) || (rw.raw_scale && (!a.dL_dscale || !a.dL_drot)))
-        return fail(FRG_EINVAL, "null gradient output for a provided input");
-    if (a.workspace_bytes < frg_backward_workspace_bytes(P, R) || !workspace)
-        return fail(FRG_EALLOC, "workspace too small: need %zu bytes", frg_backward_workspace_bytes(P, R));
-    // R sizes the slots and the backward blend's item list: fewer than the forward rendered would overrun them.  (More is
-    // fine -- a deferred forward's capacity: where the forward's checkpoints lie in the binning chunk is taken from what the
-    // forward stamped, Counters::carved_R, not from R.)
-    // The arithmetic of this backward's blend pass (the backward recomputes its forward's alpha, T and contributor tests: the
-    // same arithmetic keeps them consistent) and whether that forward kept anything for a backward were stamped into the
-    // image chunk by the forward's blend kernel (Counters::fwd_flags): they travel with the buffers.  The host's notes are
-    // keyed by ADDRESS -- a buffer copied to an address some earlier forward used would inherit that forward's note -- so
-    // they decide nothing a stamp can contradict:
-    //   * arithmetic: what the caller states (frg_backward_args::exact_blend; the Python layer carries it in its autograd
-    //     ctx), else BOTH instantiations are launched and each leaves at once unless the stamp names it (exact = -1 below);
-    //   * forward_only: a note that says "an ordinary forward" lets the call through (a forward_only stamp then still leaves
-    //     the kernels without work); anything else -- no note, or a note that says forward_only -- is settled by reading the
-    //     stamp back, one blocking copy of the forward's counters, which also tells the arithmetic.
-    //   * R: a note that says the forward rendered MORE instances than this call's R (slots and item lists would overrun) is
-    //     checked against the stamped count the same way before the call is refused.
-    int exact = a.exact_blend == 0 ? -1 : FwdModes::pick(a.exact_blend, 1, 0);
-    const std::optional<FwdNote> note = g_fwd_notes.find(geom_buffer);
-    if ((!note || note->fwd_only || (note->rendered >= 0 && R < note->rendered)) && phase != 2) {
-        frg::Counters* host = pinned_counters();
-        if (!host) return fail(FRG_EHIP, "hipHostMalloc failed");
-        const frg::ImageState img0 = frg::ImageState::carve(image_buffer, width, height, false);
-        FRG_HIP(hipMemcpyAsync(host, img0.counters, sizeof(frg::Counters), hipMemcpyDeviceToHost, stream));
-        FRG_HIP(hipStreamSynchronize(stream));
-        const uint32_t flags = host->fwd_flags;
-        if (!(flags & FRG_FWD_STAMPED))
-            return fail(FRG_EINVAL, "the image buffer carries no forward's stamp: these are not the buffers of a completed frg_forward");
-        if (flags & FRG_FWD_ONLY)
-            return fail(FRG_EINVAL, "the forward that filled these buffers was called with forward_only = 1: it kept nothing for a backward");
-        if ((uint32_t)R < host->num_rendered)
-            return fail(FRG_EINVAL, "R = %d, but the forward that filled this geometry buffer rendered %u instances", R, host->num_rendered);
-        if (exact < 0) exact = (flags & FRG_FWD_EXACT) ? 1 : 0;
-    }
-
-    // Nothing here depends on the process-wide binning options: every field of the three chunks that the
-    // backward reads is carved from (P, W, H, R) alone (the option-dependent matrices of the binning stage
-    // come last in the image chunk), and the kernels take the forward's binning mode from the counters it
-    // stamped.  "exact_blend" only selects the arithmetic of this backward's own blend pass.
-    frg::ViewParams vp = make_view(P, a.D, a.M, width, height, a.tan_fovx, a.tan_fovy, a.scale_modifier, 0);
-    const frg::GeomState g = frg::GeomState::carve(geom_buffer, P);
-    const frg::ImageState img = frg::ImageState::carve(image_buffer, width, height, false);
-    const frg::BinningState b = frg::BinningState::carve(a.binning_buffer, R, 0);
-    float* slots = reinterpret_cast<float*>(workspace);
-    float* sums = reinterpret_cast<float*>(workspace + slots_bytes(R));
-    unsigned long long* live_masks = phase == 1 ? reinterpret_cast<unsigned long long*>(workspace + slots_bytes(R) + sums_bytes(P)) : nullptr;
-    float* dir_terms = reinterpret_cast<float*>(workspace + slots_bytes(R) + sums_bytes(P) + live_mask_bytes(P) + pack_scratch_bytes(P));
-    if (phase < 0 || phase > 2) return fail(FRG_EINVAL, "frg_backward_args: phase %d (0 whole | 1 blend + slot sums | 2 the rest)", phase);
-    const int* const radii = a.radii ? a.radii : g.internal_radii;   // rasterizer_impl.cu:375-377
-
-    frg::FwdInputs in{means3D, scales, a.rotations, nullptr, shs, a.cov3D_precomp, a.colors_precomp, a.viewmatrix, a.projmatrix, a.campos};
-    in.raw = rw;
-    frg::BwdOutputs out{a.dL_dmean2D, a.dL_dconic, a.dL_dopacity, a.dL_dcolor, a.dL_dmean3D, a.dL_dcov3D, a.dL_dsh, a.dL_dscale, a.dL_drot};
-    out.dL_dshell_logits = a.dL_dshell_logits;
-    out.dL_dshell_verts = a.dL_dshell_cell_verts;
-    out.row_live = a.row_live;
-    const int pbw_flags = phase == 1 ? FRG_PBW_SUMS_ONLY : phase == 2 ? FRG_PBW_FROM_SUMS : 0;
-    // the per-Gaussian backward: each call site states its flags, its form (heavy_only), its stream and, in phase 1, what it leaves
-    auto preprocess_bwd = [&](int flags, bool heavy_only, hipStream_t s, unsigned long long* masks = nullptr, float* dirs = nullptr,
-                              int range_first = 0, int range_count = 0) {
-        return frg::launch_preprocess_bwd(P, vp, in, radii, g, img, slots, out, g_ablate.load(), flags, heavy_only, s, sums, masks, dirs,
-                                          range_first, range_count);
-    };
-    if (phase == 2) {     // the sums are in the workspace: one launch, no slot reduction, hence no 16-wave form either
-        if (!phase1_matches(workspace, geom_buffer, image_buffer, P, R))
-            return fail(FRG_EINVAL, "backward phase 2 without a matching phase 1 on this workspace (same P, R, geometry and image buffers)");
-        StageScope sc_(ST_PREPROCESS_BWD, stream);
-        FRG_STAGE(preprocess_bwd(pbw_flags | FRG_PBW_NO_HEAVY_LAUNCH, false, stream), "preprocess_bwd (phase 2)");
-        return FRG_OK;
-    }
-    if (phase == 1) note_phase1(workspace, geom_buffer, image_buffer, P, R);
-    const bool ranged = a.range_count > 0;
-    if (ranged) {
-        if (phase != 1) return fail(FRG_EINVAL, "frg_backward_args: a range is offered with phase 1 only (phase %d)", phase);
-        if (a.range_first < 0 || a.range_first % 256 != 0 || (long long)a.range_first + a.range_count > P)
-            return fail(FRG_EINVAL, "frg_backward_args: range [%d, +%d) of %d Gaussians (range_first: a multiple of 256)", a.range_first, a.range_count, P);
-    }
-    const bool probe_bwd = (g_probe.load() & 2) && g_probe_side.ensure();
-    if (probe_bwd) {   // timing experiment: the per-Gaussian backward beside the blend (it reads the previous frame's slots)
-        FRG_HIP(g_probe_side.fork_from(stream));
-        FRG_HIP(preprocess_bwd(pbw_flags, false, g_probe_side.stream));
-        FRG_HIP(preprocess_bwd(pbw_flags, true, g_probe_side.stream));
-        FRG_HIP(hipEventRecord(g_probe_side.join, g_probe_side.stream));
-    }
-    if (!ranged || a.range_first == 0) {
-        StageScope sc_(ST_BLEND_BWD, stream);
-        if (exact != 0)
-            FRG_STAGE(frg::launch_blend_bwd_exact(vp, g, img, b, background, dL_dpix, slots, (uint32_t)R, g_bwd_batch.load(), stream, exact < 0), "blend_bwd");
-        if (exact <= 0)
-            FRG_STAGE(frg::launch_blend_bwd_fast(vp, g, img, b, background, dL_dpix, slots, (uint32_t)R, g_bwd_batch.load(), stream, exact < 0), "blend_bwd");
-    }
-    if (probe_bwd) { FRG_HIP(hipStreamWaitEvent(stream, g_probe_side.join, 0)); return FRG_OK; }
-    if (ranged) {      // phase 1 in pieces: the plain kernel over this range, whatever its waves own (no 16-wave side launch)
-        StageScope sc_(ST_PREPROCESS_BWD, stream);
-        FRG_STAGE(preprocess_bwd(pbw_flags | FRG_PBW_NO_HEAVY_LAUNCH, false, stream, live_masks, dir_terms, a.range_first, a.range_count), "preprocess_bwd (phase 1, range)");
-        return FRG_OK;
-    }
-    {
-        // the 16-wave form for the Gaussians that own thousands of slots runs on a side stream beside the plain kernel
-        // (usually its workgroups find an empty list and leave)
-        StageScope sc_(ST_PREPROCESS_BWD, stream);
-        // the forward's scatter posted how many waves of Gaussians need the 16-wave form (Mailbox::heavy): none, usually
-        const int heavy = g_assume_no_heavy.load(std::memory_order_relaxed) ? 0 : debug || !note ? -1 : note->heavy_waves_posted();
-        const bool skip_heavy = heavy == 0;
-        const bool side = !skip_heavy && !debug && g_bwd_side.ensure();
-        // Known to exist: the few 16-wave workgroups go on the CALLER's stream and start at once on an empty GPU, the
-        // plain kernel follows on the side stream a cross-queue hop later and fills the rest -- behind the plain kernel's
-        // 47 k waves the 1024-thread workgroups waited for a whole free CU and ran mostly after it (clustered scene:
-        // 0.41 -> 0.33 ms).  Unknown (no post): the 16-wave form on the high-priority side stream, as before.
-        const bool heavy_first = side && heavy > 0 && g_bwd_heavy_first.load(std::memory_order_relaxed);
-        hipStream_t hs = side ? g_bwd_side.stream : stream;
-        hipStream_t s_heavy = heavy_first ? stream : hs, s_plain = heavy_first ? hs : stream;
-        if (side) FRG_HIP(g_bwd_side.fork_from(stream));
-        if (!skip_heavy)
-            FRG_STAGE(preprocess_bwd(pbw_flags, true, s_heavy, live_masks, dir_terms), "preprocess_bwd (long runs)");
-        FRG_STAGE(preprocess_bwd(pbw_flags | (skip_heavy ? FRG_PBW_NO_HEAVY_LAUNCH : 0), false, s_plain, live_masks, dir_terms), "preprocess_bwd");
-        if (side) { FRG_HIP(hipEventRecord(g_bwd_side.join, hs)); FRG_HIP(hipStreamWaitEvent(stream, g_bwd_side.join, 0)); }
-    }
-    return FRG_OK;
-}
-
-extern "C" {
-
 int frg_backward(int P, int D, int M, int R, const float* background, int width, int height,
                  const float* means3D, const float* shs, const float* colors_precomp,
                  const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
@@ -1038,384 +1142,6 @@ int frg_backward_ex(const frg_backward_args* a)
         return fail(FRG_EINVAL, "frg_backward_args: struct_size %zu, this library expects %zu (or %zu, %zu, %zu, %zu)", a ? a->struct_size : (size_t)0,
                     sizeof(frg_backward_args), b4, b3, b2, b1);
     return backward_impl(full);
-}
-
-int frg_sh_color_grad(int P, const char* geom_buffer, const int* radii, const float* dL_dcolors,
-                      float* out_drgb, void* hip_stream)
-{
-    if (P < 0) return fail(FRG_EINVAL, "P < 0");
-    if (P == 0) return FRG_OK;
-    if (!geom_buffer || !radii || !dL_dcolors || !out_drgb) return fail(FRG_EINVAL, "null pointer");
-    const frg::GeomState g = frg::GeomState::carve(const_cast<char*>(geom_buffer), P);
-    FRG_HIP(frg::launch_sh_color_grad(P, g, radii, dL_dcolors, out_drgb, (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-int frg_sh_grad_from_views(int P, int D, int M, int n_views, const float* means3D,
-                           const float* campos, long long campos_stride,
-                           const float* drgb, long long view_stride, float* dL_dsh, void* hip_stream)
-{
-    if (P < 0 || n_views < 0 || D < 0 || D > 3) return fail(FRG_EINVAL, "bad sizes P=%d views=%d D=%d", P, n_views, D);
-    if (M < (D + 1) * (D + 1)) return fail(FRG_EINVAL, "degree %d needs %d coefficients, got M=%d", D, (D + 1) * (D + 1), M);
-    if (P == 0) return FRG_OK;
-    if (!means3D || !dL_dsh || (n_views > 0 && (!campos || !drgb))) return fail(FRG_EINVAL, "null pointer");
-    FRG_HIP(frg::launch_sh_grad_from_views(P, D, M, n_views, means3D, campos, campos_stride, drgb, view_stride, dL_dsh,
-                                           (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-int frg_pack_grad_rows(int P, const float* dL_dmeans3D, const float* dL_dscales, const float* dL_drotations, const float* dL_dopacity,
-                       const float* drgb, float* rows, long long capacity_rows, unsigned int* count, void* hip_stream)
-{
-    if (P < 0 || capacity_rows < 0 || capacity_rows > 0xffffffffLL) return fail(FRG_EINVAL, "bad sizes P=%d capacity=%lld", P, capacity_rows);
-    if (!count) return fail(FRG_EINVAL, "null pointer");
-    if (P == 0) { FRG_HIP(hipMemsetAsync(count, 0, sizeof(unsigned int), (hipStream_t)hip_stream)); return FRG_OK; }
-    if (!dL_dmeans3D || !dL_dscales || !dL_drotations || !dL_dopacity || !drgb || (!rows && capacity_rows > 0)) return fail(FRG_EINVAL, "null pointer");
-    if (reinterpret_cast<uintptr_t>(rows) % 16 != 0) return fail(FRG_EINVAL, "rows must be 16-byte aligned");
-    FRG_HIP(frg::launch_pack_grad_rows(P, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacity, drgb, rows, (unsigned int)capacity_rows, count,
-                                       (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-int frg_scatter_grad_rows(long long n_rows, int P, const float* rows, float* dL_dmeans3D, float* dL_dscales, float* dL_drotations,
-                          float* dL_dopacity, float* drgb_dense, void* hip_stream)
-{
-    if (P < 0 || n_rows < 0 || n_rows > 0xffffffffLL) return fail(FRG_EINVAL, "bad sizes P=%d rows=%lld", P, n_rows);
-    if (n_rows == 0 || P == 0) return FRG_OK;
-    if (!rows || !dL_dmeans3D || !dL_dscales || !dL_drotations || !dL_dopacity) return fail(FRG_EINVAL, "null pointer");
-    if (reinterpret_cast<uintptr_t>(rows) % 16 != 0) return fail(FRG_EINVAL, "rows must be 16-byte aligned");
-    FRG_HIP(frg::launch_scatter_grad_rows((unsigned int)n_rows, P, rows, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacity, drgb_dense,
-                                          (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-size_t frg_sum_packet_bytes(int n_gaussians, long long capacity_rows)
-{
-    if (n_gaussians < 0 || capacity_rows < 0) return 0;
-    return frg::sum_packet_bytes((size_t)n_gaussians, (size_t)capacity_rows);
-}
-
-int frg_pack_sum_rows(int P, int R, int first, int count, char* workspace, size_t workspace_bytes, const float* drgb_masked,
-                      const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                      int width, int height, float scale_modifier, int D, void* packet, size_t packet_bytes, long long capacity_rows,
-                      void* hip_stream)
-{
-    if (P < 0 || R < 0 || first < 0 || count < 0 || (long long)first + count > P || first % 64 != 0)
-        return fail(FRG_EINVAL, "bad range: P=%d first=%d (a multiple of 64) count=%d", P, first, count);
-    if (capacity_rows < 0 || capacity_rows > 0x7fffffffLL) return fail(FRG_EINVAL, "capacity_rows %lld", capacity_rows);
-    if (!workspace || workspace_bytes < frg_backward_workspace_bytes(P, R)) return fail(FRG_EALLOC, "not the workspace of a backward with P=%d R=%d", P, R);
-    if (!packet || packet_bytes < frg_sum_packet_bytes(count, capacity_rows) || reinterpret_cast<uintptr_t>(packet) % 16 != 0)
-        return fail(FRG_EALLOC, "packet: need %zu bytes, 16-byte aligned", frg_sum_packet_bytes(count, capacity_rows));
-    if (!drgb_masked || !viewmatrix || !projmatrix || !campos) return fail(FRG_EINVAL, "null pointer");
-    if (width <= 0 || height <= 0 || D < 0 || D > 3) return fail(FRG_EINVAL, "bad view: %dx%d degree %d", width, height, D);
-    const float* sums = reinterpret_cast<const float*>(workspace + slots_bytes(R));
-    const unsigned long long* masks = reinterpret_cast<const unsigned long long*>(workspace + slots_bytes(R) + sums_bytes(P));
-    uint32_t* group_tot = reinterpret_cast<uint32_t*>(workspace + slots_bytes(R) + sums_bytes(P) + live_mask_bytes(P));
-    const float* dir_terms = reinterpret_cast<const float*>(workspace + slots_bytes(R) + sums_bytes(P) + live_mask_bytes(P) + pack_scratch_bytes(P));
-    const frg::SumCamera cam{tan_fovx, tan_fovy, scale_modifier, width, height, D};
-    FRG_HIP(frg::launch_pack_sum_rows(first, count, (uint32_t)capacity_rows, masks, sums, dir_terms, drgb_masked, cam, viewmatrix, projmatrix, campos, packet,
-                                      group_tot, (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-size_t frg_combine_workspace_bytes(int n_views, long long capacity_rows)
-{
-    if (n_views < 0 || capacity_rows < 0) return 0;
-    return frg::combine_workspace_bytes(n_views, (size_t)capacity_rows);
-}
-
-int frg_backward_combine(const frg_combine_args* a)
-{
-    if (!a || a->struct_size != sizeof(frg_combine_args))
-        return fail(FRG_EINVAL, "frg_combine_args: struct_size %zu, this library expects %zu", a ? a->struct_size : (size_t)0, sizeof(frg_combine_args));
-    if (a->P < 0 || a->first < 0 || a->count < 0 || (long long)a->first + a->count > a->P || a->first % 64 != 0)
-        return fail(FRG_EINVAL, "bad range: P=%d first=%d (a multiple of 64) count=%d", a->P, a->first, a->count);
-    if (a->n_views < 1 || a->n_views > 16) return fail(FRG_EINVAL, "1..16 views expected, got %d", a->n_views);
-    if (a->M != 16) return fail(FRG_EINVAL, "the combine pass takes SH rows of 16 coefficients (M = %d)", a->M);
-    if (a->capacity_rows >= 65535LL * 256) return fail(FRG_EINVAL, "capacity_rows %lld: a packet holds fewer than 2^24 rows (cut the Gaussians into more ranges)", a->capacity_rows);
-    if (a->count == 0) return FRG_OK;
-    if (!a->packets || a->packet_stride_bytes % 16 != 0 || a->packet_stride_bytes < frg_sum_packet_bytes(a->count, a->capacity_rows))
-        return fail(FRG_EINVAL, "packets: stride %zu, a packet of %d Gaussians and %lld rows has %zu bytes", a->packet_stride_bytes, a->count,
-                    a->capacity_rows, frg_sum_packet_bytes(a->count, a->capacity_rows));
-    if ((a->means3D == nullptr) || !a->shs) return fail(FRG_EINVAL, "means3D and shs are required (shell-bound centres are not offered here)");
-    if (!a->workspace || a->workspace_bytes < frg_combine_workspace_bytes(a->n_views, a->capacity_rows) || reinterpret_cast<uintptr_t>(a->workspace) % 16 != 0)
-        return fail(FRG_EALLOC, "workspace: need %zu bytes, 16-byte aligned", frg_combine_workspace_bytes(a->n_views, a->capacity_rows));
-    if ((a->opacities == nullptr) == (a->raw_opacities == nullptr)) return fail(FRG_EINVAL, "provide exactly one of opacities / raw_opacities");
-    const bool raw_sr = a->raw_scales && a->raw_rotations;
-    if (raw_sr == (a->scales && a->rotations) || (a->raw_scales == nullptr) != (a->raw_rotations == nullptr) || (a->scales == nullptr) != (a->rotations == nullptr))
-        return fail(FRG_EINVAL, "provide (scales, rotations) or (raw_scales, raw_rotations)");
-    if (!a->dL_dmean3D || !a->dL_dscale || !a->dL_drot || !a->dL_dopacity || !a->dL_dsh) return fail(FRG_EINVAL, "null gradient output");
-    if ((reinterpret_cast<uintptr_t>(a->shs) | reinterpret_cast<uintptr_t>(a->dL_dsh) | reinterpret_cast<uintptr_t>(a->dL_drot) |
-         reinterpret_cast<uintptr_t>(a->rotations) | reinterpret_cast<uintptr_t>(a->packets)) % 16 != 0)
-        return fail(FRG_EINVAL, "shs, rotations, dL_dsh, dL_drot and the packets must be 16-byte aligned");
-    frg::FwdInputs in{a->means3D, a->scales, a->rotations, a->opacities, a->shs, nullptr, nullptr, nullptr, nullptr, nullptr};
-    in.raw.raw_opacity = a->raw_opacities; in.raw.raw_scale = a->raw_scales; in.raw.raw_rot = a->raw_rotations;
-    frg::BwdOutputs out{nullptr, nullptr, a->dL_dopacity, nullptr, a->dL_dmean3D, nullptr, a->dL_dsh, a->dL_dscale, a->dL_drot};
-    FRG_HIP(frg::launch_backward_combine(a->first, a->count, a->n_views, a->packets, a->packet_stride_bytes, (uint32_t)a->capacity_rows, in, out,
-                                         a->status, a->status_seq, a->row_live, a->workspace, (hipStream_t)a->hip_stream));
-    return FRG_OK;
-}
-
-static thread_local frg::AdamRows g_adam_rows;     // set by frg_adam_step_rows around its call of frg_adam_step
-static thread_local bool g_adam_shard = false;     // frg_adam_step_shard: segment ends before the first element (negative) are expected
-
-int frg_adam_step(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                  const long long* segment_ends, const float* segment_lrs, const int* segment_period,
-                  const int* segment_head, const float* segment_head_lrs, int n_segments,
-                  double beta1, double beta2, double eps, int step, float grad_scale, void* hip_stream)
-{
-    if (n < 0 || step < 1) return fail(FRG_EINVAL, "bad sizes n=%lld step=%d", n, step);
-    if (n_segments < 1 || n_segments > FRG_ADAM_MAX_SEGMENTS || !segment_ends || !segment_lrs)
-        return fail(FRG_EINVAL, "1..%d segments expected, got %d", FRG_ADAM_MAX_SEGMENTS, n_segments);
-    for (int k = 1; k < n_segments; k++)
-        if (segment_ends[k] < segment_ends[k - 1]) return fail(FRG_EINVAL, "segment ends must not decrease");
-    if ((segment_ends[0] < 0 && !g_adam_shard) || segment_ends[n_segments - 1] != n) return fail(FRG_EINVAL, "the last segment must end at n");
-    if (n == 0) return FRG_OK;
-    if (!params || !grads || !exp_avg || !exp_avg_sq) return fail(FRG_EINVAL, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
-         reinterpret_cast<uintptr_t>(exp_avg_sq)) % 16 != 0)
-        return fail(FRG_EINVAL, "the four arrays must be 16-byte aligned");
-    if ((n + 3) / 4 / 256 + 1 > 0x7fffffffLL) return fail(FRG_EINVAL, "n too large for one launch");
-    // Python-float arithmetic of torch/optim/adam.py: doubles, rounded to float where a tensor op takes them
-    const double bc1 = 1.0 - std::pow(beta1, (double)step);
-    const double bc2 = 1.0 - std::pow(beta2, (double)step);
-    frg::AdamSegments seg;
-    seg.count = n_segments;
-    for (int k = 0; k < FRG_ADAM_MAX_SEGMENTS; k++) {
-        seg.end[k] = k < n_segments ? segment_ends[k] : n;
-        seg.step_size[k] = k < n_segments ? (float)((double)segment_lrs[k] / bc1) : 0.0f;
-        const bool sub = k < n_segments && segment_period && segment_head && segment_head_lrs && segment_period[k] > 0;
-        if (sub && (segment_head[k] < 0 || segment_head[k] > segment_period[k]))
-            return fail(FRG_EINVAL, "segment %d: head %d outside its period %d", k, segment_head[k], segment_period[k]);
-        seg.period[k] = sub ? segment_period[k] : 0;
-        seg.head[k] = sub ? segment_head[k] : 0;
-        seg.head_step_size[k] = sub ? (float)((double)segment_head_lrs[k] / bc1) : 0.0f;
-    }
-    const float w1 = (float)(1.0 - beta1);      // betas arrive as doubles: 1 - beta is formed before rounding to float,
-    const float omb2 = (float)(1.0 - beta2);    // as the Python floats of torch/optim/adam.py are
-    const float inv_bc2_sqrt = 1.0f / (float)std::sqrt(bc2);   // ATen divides by a scalar as a multiplication by its float reciprocal
-    FRG_HIP(frg::launch_adam_step(n, params, grads, exp_avg, exp_avg_sq, seg, w1, (float)beta2, omb2, inv_bc2_sqrt, (float)eps, grad_scale,
-                                  (hipStream_t)hip_stream, g_adam_rows.live ? &g_adam_rows : nullptr));
-    return FRG_OK;
-}
-
-int frg_adam_step_shard(long long n, long long first, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                        const long long* segment_ends, const float* segment_lrs, const int* segment_period,
-                        const int* segment_head, const float* segment_head_lrs, int n_segments,
-                        double beta1, double beta2, double eps, int step, float grad_scale, void* hip_stream)
-{
-    // elements [first, first + n) of the flat layout, the four arrays pointing at element `first`: the segment table is
-    // shifted by `first` behind a zero-length segment that ends at -first -- the kernel takes an element's segment as the last
-    // one whose predecessor ends at or before it and its offset from that end, so negative ends give every element of the
-    // shard its true segment and its true phase inside it (the DC / rest split of the SH rows)
-    if (n < 0 || first < 0 || first % 4 != 0) return fail(FRG_EINVAL, "bad shard: n=%lld first=%lld (a multiple of 4 elements)", n, first);
-    if (n_segments < 1 || n_segments + 1 > FRG_ADAM_MAX_SEGMENTS || !segment_ends || !segment_lrs)
-        return fail(FRG_EINVAL, "a sharded step takes 1..%d segments, got %d", FRG_ADAM_MAX_SEGMENTS - 1, n_segments);
-    if (first + n > segment_ends[n_segments - 1]) return fail(FRG_EINVAL, "the shard ends behind the last segment");
-    long long ends[FRG_ADAM_MAX_SEGMENTS];
-    float lrs[FRG_ADAM_MAX_SEGMENTS], hlrs[FRG_ADAM_MAX_SEGMENTS];
-    int per[FRG_ADAM_MAX_SEGMENTS], head[FRG_ADAM_MAX_SEGMENTS];
-    ends[0] = -first; lrs[0] = 0.0f; hlrs[0] = 0.0f; per[0] = 0; head[0] = 0;
-    for (int k = 0; k < n_segments; k++) {
-        ends[k + 1] = segment_ends[k] - first;
-        lrs[k + 1] = segment_lrs[k];
-        per[k + 1] = segment_period ? segment_period[k] : 0;
-        head[k + 1] = segment_head ? segment_head[k] : 0;
-        hlrs[k + 1] = segment_head_lrs ? segment_head_lrs[k] : 0.0f;
-    }
-    ends[n_segments] = n;       // the shard ends inside (or at the end of) the last segment it reaches; later ones are cut off
-    for (int k = 1; k <= n_segments; k++) if (ends[k] > n) ends[k] = n;
-    g_adam_shard = true;
-    const int rc = frg_adam_step(n, params, grads, exp_avg, exp_avg_sq, ends, lrs, per, head, hlrs, n_segments + 1, beta1, beta2, eps, step,
-                                 grad_scale, hip_stream);
-    g_adam_shard = false;
-    return rc;
-}
-
-int frg_adam_step_rows(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                       const long long* segment_ends, const float* segment_lrs, const int* segment_period,
-                       const int* segment_head, const float* segment_head_lrs, int n_segments,
-                       double beta1, double beta2, double eps, int step, float grad_scale,
-                       const unsigned char* row_live, int P, const int* segment_width, void* hip_stream)
-{
-    if (!row_live) return frg_adam_step(n, params, grads, exp_avg, exp_avg_sq, segment_ends, segment_lrs, segment_period, segment_head,
-                                        segment_head_lrs, n_segments, beta1, beta2, eps, step, grad_scale, hip_stream);
-    if (P < 0 || !segment_width) return fail(FRG_EINVAL, "row_live needs P >= 0 and segment_width");
-    if (n_segments < 1 || n_segments > FRG_ADAM_MAX_SEGMENTS) return fail(FRG_EINVAL, "1..%d segments expected, got %d", FRG_ADAM_MAX_SEGMENTS, n_segments);
-    for (int k = 0; k < n_segments; k++) {
-        const long long begin = k ? segment_ends[k - 1] : 0;
-        if (segment_width[k] < 0 || (long long)segment_width[k] * P > segment_ends[k] - begin)
-            return fail(FRG_EINVAL, "segment %d: %d elements per Gaussian x %d Gaussians exceed its %lld elements", k, segment_width[k], P, segment_ends[k] - begin);
-        if (segment_width[k] > 0 && segment_ends[k] - begin > 0xffffffffLL)
-            return fail(FRG_EINVAL, "segment %d: a per-Gaussian segment of a masked step holds at most 2^32 elements", k);
-        // the kernel takes four consecutive elements per thread and lets ONE mask look-up stand for all four when the rows of
-        // their segment are a multiple of four elements long: true only if the segment starts on a multiple of four elements
-        if (segment_width[k] > 0 && segment_width[k] % 4 == 0 && begin % 4 != 0)
-            return fail(FRG_EINVAL, "segment %d: rows of %d elements must begin on a multiple of 4 elements (begins at %lld)", k, segment_width[k], begin);
-    }
-    g_adam_rows.live = row_live; g_adam_rows.P = P;
-    for (int k = 0; k < FRG_ADAM_MAX_SEGMENTS; k++) {
-        g_adam_rows.width[k] = k < n_segments ? segment_width[k] : 0;
-        g_adam_rows.magic[k] = g_adam_rows.width[k] > 1 ? (unsigned int)(0x100000000ull / (unsigned long long)g_adam_rows.width[k]) : 0u;
-    }
-    const int rc = frg_adam_step(n, params, grads, exp_avg, exp_avg_sq, segment_ends, segment_lrs, segment_period, segment_head,
-                                 segment_head_lrs, n_segments, beta1, beta2, eps, step, grad_scale, hip_stream);
-    g_adam_rows.live = nullptr;
-    return rc;
-}
-
-size_t frg_photometric_workspace_bytes(int channels, int width, int height)
-{
-    if (channels <= 0 || width <= 0 || height <= 0) return 0;
-    return frg::photometric_workspace_bytes(channels, width, height);
-}
-
-int frg_photometric_loss(int channels, int width, int height, const float* image, const float* target,
-                         const float* window11, float lambda_dssim, float* loss, float* dL_dimage,
-                         char* workspace, size_t workspace_bytes, void* hip_stream)
-{
-    if (channels <= 0 || width <= 0 || height <= 0) return fail(FRG_EINVAL, "bad sizes C=%d W=%d H=%d", channels, width, height);
-    if (!image || !target || !window11 || !loss) return fail(FRG_EINVAL, "null pointer");
-    if (!workspace || workspace_bytes < frg_photometric_workspace_bytes(channels, width, height))
-        return fail(FRG_EALLOC, "workspace too small: need %zu bytes", frg_photometric_workspace_bytes(channels, width, height));
-    if ((long long)channels * ((width + 15) / 16) * ((height + 15) / 16) > 0x7fffffffLL) return fail(FRG_EINVAL, "image too large");
-    FRG_HIP(frg::launch_photometric(channels, width, height, image, target, window11, lambda_dssim, loss, dL_dimage, workspace,
-                                    (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-int frg_activate(int P, const float* raw_opacity, const float* raw_scale, const float* raw_rot,
-                 float* opacity, float* scale, float* rot, void* hip_stream)
-{
-    if (P < 0) return fail(FRG_EINVAL, "P < 0");
-    if (P == 0) return FRG_OK;
-    if (!raw_opacity || !raw_scale || !raw_rot || !opacity || !scale || !rot) return fail(FRG_EINVAL, "null pointer");
-    FRG_HIP(frg::launch_activate(P, raw_opacity, raw_scale, raw_rot, opacity, scale, rot, (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-int frg_activate_backward(int P, const float* opacity, const float* scale, const float* raw_rot,
-                          float* g_opacity, float* g_scale, float* g_rot, void* hip_stream)
-{
-    if (P < 0) return fail(FRG_EINVAL, "P < 0");
-    if (P == 0) return FRG_OK;
-    if (!opacity || !scale || !raw_rot || !g_opacity || !g_scale || !g_rot) return fail(FRG_EINVAL, "null pointer");
-    FRG_HIP(frg::launch_activate_bwd(P, opacity, scale, raw_rot, g_opacity, g_scale, g_rot, (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-size_t frg_knn_workspace_bytes(int P) { return P > 0 ? frg::knn_workspace_bytes(P) : 0; }
-
-int frg_knn_mean_dist2(int P, const float* points, float* mean_dist2, char* workspace, size_t workspace_bytes, void* hip_stream)
-{
-    if (P < 0) return fail(FRG_EINVAL, "P < 0");
-    if (P == 0) return FRG_OK;
-    if (!points || !mean_dist2) return fail(FRG_EINVAL, "null pointer");
-    if (!workspace || workspace_bytes < frg_knn_workspace_bytes(P))
-        return fail(FRG_EALLOC, "workspace too small: need %zu bytes", frg_knn_workspace_bytes(P));
-    if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return fail(FRG_EINVAL, "workspace must be 256-byte aligned");
-    FRG_HIP(frg::launch_knn(P, points, mean_dist2, workspace, (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-int frg_shell_points(int P, const float* bary_logits, const float* cell_verts, const long long* point_cell_indices,
-                     float* points, void* hip_stream)
-{
-    if (P < 0) return fail(FRG_EINVAL, "P < 0");
-    if (P == 0) return FRG_OK;
-    if (!bary_logits || !cell_verts || !point_cell_indices || !points) return fail(FRG_EINVAL, "null pointer");
-    FRG_HIP(frg::launch_shell_points(P, bary_logits, cell_verts, point_cell_indices, points, (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-int frg_shell_points_backward(int P, const float* bary_logits, const float* cell_verts, const long long* point_cell_indices,
-                              const float* dL_dpoints, float* dL_dlogits, void* hip_stream)
-{
-    if (P < 0) return fail(FRG_EINVAL, "P < 0");
-    if (P == 0) return FRG_OK;
-    if (!bary_logits || !cell_verts || !point_cell_indices || !dL_dpoints || !dL_dlogits) return fail(FRG_EINVAL, "null pointer");
-    FRG_HIP(frg::launch_shell_points_bwd(P, bary_logits, cell_verts, point_cell_indices, dL_dpoints, dL_dlogits,
-                                         (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-// ---- adaptive density control (densify.hip) ----
-int frg_densify_accumulate(int P, const int* radii, const float* dL_dmean2D, const unsigned char* row_live,
-                           float* xyz_gradient_accum, float* denom, float* max_radii2D, void* hip_stream)
-{
-    if (P < 0) return fail(FRG_EINVAL, "P < 0");
-    if (P == 0) return FRG_OK;
-    if (!radii || !dL_dmean2D || !xyz_gradient_accum || !denom || !max_radii2D) return fail(FRG_EINVAL, "null pointer");
-    FRG_HIP(frg::launch_densify_accumulate(P, radii, dL_dmean2D, row_live, xyz_gradient_accum, denom, max_radii2D,
-                                           (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-size_t frg_densify_workspace_bytes(int P) { return P > 0 ? frg::densify_workspace_bytes(P) : 0; }
-
-int frg_densify_plan(int P, const float* raw_scales, const float* raw_opacities, const float* xyz_gradient_accum,
-                     const float* denom, const frg_densify_params* params, int* plan, int* record,
-                     char* workspace, size_t workspace_bytes, void* hip_stream)
-{
-    if (P <= 0) return fail(FRG_EINVAL, "P = %d: a model to densify has Gaussians", P);
-    if (P > 0x7fffffff / 3) return fail(FRG_EINVAL, "P = %d: up to 3 P resulting rows must fit 31 bits", P);
-    if (!params || params->struct_size < sizeof(frg_densify_params)) return fail(FRG_EINVAL, "frg_densify_params: struct_size");
-    if (!raw_scales || !raw_opacities || !xyz_gradient_accum || !denom || !plan || !record) return fail(FRG_EINVAL, "null pointer");
-    if (!workspace || workspace_bytes < frg_densify_workspace_bytes(P))
-        return fail(FRG_EALLOC, "workspace too small: need %zu bytes", frg_densify_workspace_bytes(P));
-    if (reinterpret_cast<uintptr_t>(workspace) % 4 != 0) return fail(FRG_EINVAL, "workspace must be 4-byte aligned");
-    // the reference compares float32 tensors with Python floats: the products are formed in double and rounded once
-    frg::DensifyThresholds t;
-    t.max_grad = (float)params->max_grad;
-    t.min_opacity = (float)params->min_opacity;
-    t.dense_scale = (float)(params->percent_dense * params->extent);
-    t.world_scale = (float)(0.1 * params->extent);
-    t.prune_world = params->prune_big_points ? 1 : 0;
-    FRG_HIP(frg::launch_densify_plan(P, raw_scales, raw_opacities, xyz_gradient_accum, denom, t, plan, record, workspace,
-                                     (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-int frg_densify_apply(int P, int P_out, const int* plan, int n_groups, const int* group_width,
-                      const long long* src_offsets, const long long* dst_offsets, long long out_numel, const float* noise,
-                      const float* params, const float* exp_avg, const float* exp_avg_sq,
-                      float* out_params, float* out_exp_avg, float* out_exp_avg_sq, void* hip_stream)
-{
-    if (P <= 0 || P_out < 0) return fail(FRG_EINVAL, "P = %d, P_out = %d", P, P_out);
-    if (n_groups < 3 || n_groups > FRG_DENSIFY_MAX_GROUPS) return fail(FRG_EINVAL, "n_groups = %d: 3 .. %d", n_groups, FRG_DENSIFY_MAX_GROUPS);
-    if (!plan || !group_width || !src_offsets || !dst_offsets || !params || !exp_avg || !exp_avg_sq) return fail(FRG_EINVAL, "null pointer");
-    if (P_out > 0 && (!out_params || !out_exp_avg || !out_exp_avg_sq)) return fail(FRG_EINVAL, "null output buffer");
-    if (group_width[0] != 3 || group_width[1] != 3 || group_width[2] != 4)
-        return fail(FRG_EINVAL, "the first three groups must be means3D [P,3], scales [P,3], rotations [P,4]");
-    frg::DensifyGroups g{};
-    g.count = n_groups;
-    g.dst_total = out_numel;
-    for (int k = 0; k < n_groups; k++) {
-        if (group_width[k] <= 0 || src_offsets[k] < 0 || dst_offsets[k] < 0 || (src_offsets[k] & 3) || (dst_offsets[k] & 3))
-            return fail(FRG_EINVAL, "group %d: width %d, offsets %lld -> %lld (offsets are multiples of 4 elements)", k, group_width[k],
-                        src_offsets[k], dst_offsets[k]);
-        const long long end = k + 1 < n_groups ? dst_offsets[k + 1] : out_numel;
-        if (dst_offsets[k] + (long long)P_out * group_width[k] > end || end - (dst_offsets[k] + (long long)P_out * group_width[k]) > 64)
-            return fail(FRG_EINVAL, "group %d: %d rows of %d elements from %lld do not end at %lld", k, P_out, group_width[k], dst_offsets[k], end);
-        if (k + 1 < n_groups && src_offsets[k] + (long long)P * group_width[k] > src_offsets[k + 1])
-            return fail(FRG_EINVAL, "group %d overlaps the next in the old layout", k);
-        g.width[k] = group_width[k];
-        g.src_offset[k] = src_offsets[k];
-        g.dst_offset[k] = dst_offsets[k];
-    }
-    if (P_out == 0) return FRG_OK;
-    FRG_HIP(frg::launch_densify_apply(P, P_out, plan, g, noise, params, exp_avg, exp_avg_sq, out_params, out_exp_avg,
-                                      out_exp_avg_sq, (hipStream_t)hip_stream));
-    return FRG_OK;
-}
-
-int frg_reset_opacity(int P, float* raw_opacities, float* exp_avg, float* exp_avg_sq, void* hip_stream)
-{
-    if (P < 0) return fail(FRG_EINVAL, "P < 0");
-    if (P == 0) return FRG_OK;
-    if (!raw_opacities || !exp_avg || !exp_avg_sq) return fail(FRG_EINVAL, "null pointer");
-    FRG_HIP(frg::launch_reset_opacity(P, raw_opacities, exp_avg, exp_avg_sq, (hipStream_t)hip_stream));
-    return FRG_OK;
 }
 
 }  // extern "C"

@@ -367,6 +367,34 @@ struct BinningState {
     }
 };
 
+// ---- backward workspace -------------------------------------------------------
+// The caller's scratch of one backward (frg_backward_workspace_bytes).  The slots are gone when the call returns; what
+// follows them is what phase 1 of a two-call backward (frg_backward_args::phase) leaves for phase 2 and for the slot-sum
+// exchange's pack (frg_pack_sum_rows).  (The backward blend's work items are listed by the forward, in its own chunks:
+// BinningState::bwd_full, ImageState::bwd_last.)
+struct BwdWorkspace {
+    float* slots;                     // FRG_SLOT_STRIDE floats (36 B) per instance
+    float* sums;                      // the nine per-Gaussian sums of the slots
+    unsigned long long* live_masks;   // one bit per Gaussian, "its sums are not all zero" (whole 256-Gaussian workgroups)
+    uint32_t* group_tot;              // the pack's scratch: one row count per group of 256 mask words
+    float* dir_terms;                 // the three view-direction terms per Gaussian of the slot-sum packets
+    size_t bytes;
+    __host__ static BwdWorkspace carve(char* base, int P, int R)
+    {
+        BwdWorkspace s;
+        const size_t Pp = (size_t)(P > 0 ? P : 1), Rr = (size_t)(R > 0 ? R : 1);
+        const size_t mask_words = Pp / 64 + 8;
+        size_t o = 0;
+        s.slots = (float*)(base + o); o = align_up(o + Rr * FRG_SLOT_STRIDE * sizeof(float), 256);
+        s.sums = (float*)(base + o); o = align_up(o + Pp * FRG_SLOT_FLOATS * sizeof(float), 256);
+        s.live_masks = (unsigned long long*)(base + o); o = align_up(o + mask_words * 8, 256);
+        s.group_tot = (uint32_t*)(base + o); o = align_up(o + (mask_words / 256 + 8) * 4, 256);
+        s.dir_terms = (float*)(base + o); o = align_up(o + Pp * 3 * sizeof(float), 256);
+        s.bytes = o;
+        return s;
+    }
+};
+
 // ---- per-view constants ------------------------------------------------------
 // Scalars travel by value; the matrices stay where the caller put them (device
 // memory, as in the reference) and are read through wave-uniform scalar loads.

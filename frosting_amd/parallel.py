@@ -932,7 +932,7 @@ class ViewParallelRasterizer:
         if self.out_color is None or tuple(self.out_color.shape) != (3, H, W):
             self.out_color = torch.empty((3, H, W), dtype=torch.float32, device=self.dev)
         # the blend arithmetic of this forward (the process option, read here) is handed to the backward explicitly: the library
-        # then launches that one instantiation instead of both behind the forward's stamp (api.hip backward_impl)
+        # then launches that one instantiation instead of both behind the forward's stamp (api.hip settle_forward_stamp)
         self._exact = int(_lib.get_option("exact_blend"))
         use_deferred = (self.deferred_counters if deferred is None else deferred) and self.capacity > 0
         if forward_only and use_deferred:

@@ -159,9 +159,8 @@ typedef struct frg_forward_args {
      * and work items of the tiles, and d(colour)/d(direction) of the SH pass: image, radii and the returned count are the
      * same bits.  frg_backward on its buffers is refused with FRG_EINVAL -- also on a copy of them at another address, and however
      * many forwards ago: the forward's blend kernel stamps "nothing kept" into the image chunk, and a backward whose host side
-     * does not remember the forward reads that stamp.  Not offered with
-     * instance_capacity > 0.  Forward alone, same process: C3 0.733 -> 0.696 ms, C2 0.0968 -> 0.0926 (the binning chunk is
-     * sized as before: the checkpoints' 8 ... 16 bytes per instance are carved and left unwritten). */
+     * does not remember the forward reads that stamp.  Not offered with instance_capacity > 0.  The binning chunk is sized
+     * as without it: the checkpoints' 8 ... 16 bytes per instance are carved and left unwritten. */
     int forward_only;
 } frg_forward_args;
 int frg_forward_ex(const frg_forward_args* args);
@@ -301,9 +300,9 @@ int frg_backward_ex(const frg_backward_args* args);
  * "sh_dir_in_backward" (default 0): 1 = the forward's SH pass does not form d(colour)/d(direction) (36 bytes stored per
  * visible Gaussian, read back by the per-Gaussian backward); a backward that follows forms it from the 192-byte SH rows of
  * the Gaussians that have a gradient, in the forward's order of additions -- every gradient bit the same.  For forward-only
- * rendering of large models (C3: the per-Gaussian forward 0.221 -> 0.189 ms); with a backward behind it the step is SLOWER
- * (+0.064 ms in the per-Gaussian backward at C3), which is why it is not the default.  M = 16 coefficients only; the backward
- * follows what its forward stamped, not the option at the time it runs.
+ * rendering of large models; with a backward behind it the step is slower, which is why it is not the default (DESIGN.md,
+ * "Measurements behind the interface").  M = 16 coefficients only; the backward follows what its forward stamped, not the
+ * option at the time it runs.
  * "fwd_order" (default 1): the forward blend takes the tiles longest list first (the size classes the scan builds for the
  * sort); 0 = in tile order, one band of tile rows per XCD.  Scheduling only, outputs bit-identical.
  * "fwd_prefetch" (default 1): the forward blend requests the next 64 list entries' records while it processes the
@@ -375,8 +374,7 @@ int frg_mesh_visible_faces(int V, int F, const float* pos, const int* tri, int w
  *   face_visible [F]   as frg_mesh_visible_faces writes it,
  *   keep [n_shell + n_background] = face_visible[cell_of_point[i]] for the shell's Gaussians, 1 for the background ones --
  * the keep_mask of frg_forward_ex.  Five launches, no host work between them: vertex transform + the clears, the two
- * z-buffer passes, the marks, the gather (the composition of torch.ones / cat / matmul, frg_mesh_visible_faces and the
- * torch index it replaces is nine launches: 105 -> 45 us per C4 frame).  The clip-space positions are one fused
+ * z-buffer passes, the marks, the gather.  The clip-space positions are one fused
  * multiply-add per term in the order of the sum; the workspace also holds them (frg_mesh_occlusion_workspace_bytes). */
 size_t frg_mesh_occlusion_workspace_bytes(int V, int F, int width, int height);
 int frg_mesh_occlusion_mask(int V, int F, const float* verts, const float* full_proj_transform, const int* tri, int width, int height,
@@ -401,7 +399,7 @@ int frg_sh_grad_from_views(int P, int D, int M, int n_views, const float* means3
                            const float* campos, long long campos_stride,
                            const float* drgb, long long view_stride, float* dL_dsh, void* hip_stream);
 
-/* Sparse form of the exchange (round 5).  Of one view's per-Gaussian gradients only the rows of Gaussians some pixel reached
+/* Sparse form of the exchange.  Of one view's per-Gaussian gradients only the rows of Gaussians some pixel reached
  * are non-zero (one visible Gaussian in seven at 3 M Gaussians), so what travels between ranks are ROWS of 16 floats
  *   { index (uint32 bit pattern), dL_dmeans3D[3], dL_dscales[3], dL_dopacity, dL_drotations[4], dRGB[3], 0 }
  * of the Gaussians with a non-zero row: 64 bytes per Gaussian with a gradient instead of 56 per Gaussian.
@@ -416,7 +414,7 @@ int frg_pack_grad_rows(int P, const float* dL_dmeans3D, const float* dL_dscales,
 int frg_scatter_grad_rows(long long n_rows, int P, const float* rows, float* dL_dmeans3D, float* dL_dscales, float* dL_drotations,
                           float* dL_dopacity, float* drgb_dense, void* hip_stream);
 
-/* Slot-sum form of the exchange (round 6).  After phase 1 of a two-call backward (frg_backward_args::phase = 1) everything a
+/* Slot-sum form of the exchange.  After phase 1 of a two-call backward (frg_backward_args::phase = 1) everything a
  * view contributes to a Gaussian's gradient is determined by the nine per-Gaussian sums that call leaves in its workspace --
  * the clamp-masked colour gradient and six pixel moments -- together with the parameters and the view's camera, which every
  * rank holds.  Only the Gaussians a pixel reached have such sums (one in eight at 3 M Gaussians).  Ranks therefore exchange

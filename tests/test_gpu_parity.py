@@ -787,7 +787,7 @@ def test_per_call_modes_of_two_rasterizers_on_two_threads(gpu_device):
 
 def test_counter_mailbox_and_copy_read_back_agree(gpu_device, ops):
     """The blocking forward learns num_rendered and the sort's class sizes from a pinned mailbox the scan workgroups
-    post to (the scatter is enqueued while the scan stage still runs; api.hip) -- option counter_mailbox = 0 restores
+    post to (the scatter is enqueued while the scan stage still runs; api.hip forward_blocking) -- option counter_mailbox = 0 restores
     the copy + stream synchronisation.  Same counters, so the same everything: views with short lists, with lists
     beyond the LDS sort (the plan kernel's fork moves), an empty view and the prefiltered assertion."""
     dev = gpu_device
