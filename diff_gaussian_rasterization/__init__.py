@@ -25,9 +25,9 @@ GaussianRasterizer, _RasterizeGaussians = make_rasterizer_class(_C)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, keep_mask=None):
+                        raster_settings, keep_mask=None, sh_rotations=None):
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, keep_mask)
+                                     cov3Ds_precomp, raster_settings, keep_mask, sh_rotations)
 
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians"]

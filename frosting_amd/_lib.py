@@ -50,7 +50,9 @@ class ForwardArgs(C.Structure):
                 ("exact_blend", C.c_int), ("tight_binning", C.c_int), ("async_sh", C.c_int),
                 ("shell_bary_mode", C.c_int),
                 # no backward will follow: nothing is kept for one
-                ("forward_only", C.c_int)]
+                ("forward_only", C.c_int),
+                # optional [P,3,3] (with shs): the SH colour of Gaussian i is evaluated at d @ R_i
+                ("sh_rotations", C.c_void_p)]
 
 
 def mode_fields(modes) -> dict:
@@ -98,7 +100,9 @@ class BackwardArgs(C.Structure):
                 # optional [P] bytes: 1 = the Gaussian has a gradient; the rows of the others are then not written
                 ("row_live", C.c_void_p),
                 # phase 1 in pieces: Gaussians [range_first, + range_count) (range_count 0: the whole phase)
-                ("range_first", C.c_int), ("range_count", C.c_int)]
+                ("range_first", C.c_int), ("range_count", C.c_int),
+                # the forward's sh_rotations (NULL exactly when it had none)
+                ("sh_rotations", C.c_void_p)]
 
 
 class CombineArgs(C.Structure):

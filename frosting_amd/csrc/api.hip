@@ -272,11 +272,12 @@ thread_local HostMail g_mail;
 // told that no backward follows.  Scheduling hints and early refusals only -- keyed by ADDRESS, a note can be stale (a buffer
 // copied to an address an earlier forward used), so nothing that decides a gradient bit hangs on one: the blend arithmetic
 // and "nothing kept" are stamped into the image chunk by the forward's blend kernel (Counters::fwd_flags) and read there
-// (settle_forward_stamp).  A ring of kFwdNotes entries (the entry of the same address is overwritten, else the next ring
+// (settle_forward_stamp); so is "the SH directions were rotated" (a note's `rotated` only decides whether the stamp is read).  A ring of kFwdNotes entries (the entry of the same address is overwritten, else the next ring
 // slot); a forgotten forward's note reads "unknown" everywhere (rendered -1, forward_only settled by the stamp, both forms
 // of the per-Gaussian backward launched as if nothing had been posted).  The pinned mailboxes are never freed.
 struct FwdNote {
     const void* geom = nullptr; const frg::Mailbox* mail = nullptr; uint32_t seq = 0; int exact = -1; int rendered = -1; bool fwd_only = false;
+    bool rotated = false;     // frg_forward_args::sh_rotations was given (the stamp: FRG_FWD_ROTATED)
     // -> the number of heavy waves the forward's scatter posted, or -1 when unknown (no post, not arrived yet, the mailbox
     // already belongs to a later forward)
     int heavy_waves_posted() const
@@ -308,11 +309,11 @@ class FwdNotes {
     }
 public:
     // a forward starts on `geom`: whatever an earlier forward posted about this buffer is void now
-    void begin(const void* geom, int exact, bool fwd_only)
+    void begin(const void* geom, int exact, bool fwd_only, bool rotated)
     {
         std::lock_guard<std::mutex> lk(mu);
         FwdNote* n = locate(geom);
-        *(n ? n : &ring[next++ % kFwdNotes]) = FwdNote{geom, nullptr, 0, exact, -1, fwd_only};
+        *(n ? n : &ring[next++ % kFwdNotes]) = FwdNote{geom, nullptr, 0, exact, -1, fwd_only, rotated};
     }
     // the forward on `geom` learnt something (its instance count, its scatter's mailbox post); a forgotten forward learns nothing
     template <class Fn>
@@ -336,18 +337,18 @@ FwdNotes g_fwd_notes;
 // does not match (an arena that grew or was reused between the calls, another frame's buffers) is refused instead of
 // producing garbage gradients.  A note decides that refusal and nothing else.
 class PhaseNotes {
-    struct Note { const void* workspace = nullptr; const void* geom = nullptr; const void* image = nullptr; int P = 0, R = 0; };
+    struct Note { const void* workspace = nullptr; const void* geom = nullptr; const void* image = nullptr; int P = 0, R = 0; bool rotated = false; };
     static constexpr int kPhaseNotes = 16;
     std::mutex mu;
     Note ring[kPhaseNotes];
     unsigned next = 0;
 public:
     // phase 1 ran on `workspace`
-    void record(const void* workspace, const void* geom, const void* image, int P, int R)
+    void record(const void* workspace, const void* geom, const void* image, int P, int R, bool rotated)
     {
         std::lock_guard<std::mutex> lk(mu);
-        for (auto& n : ring) if (n.workspace == workspace) { n = Note{workspace, geom, image, P, R}; return; }
-        ring[next++ % kPhaseNotes] = Note{workspace, geom, image, P, R};
+        for (auto& n : ring) if (n.workspace == workspace) { n = Note{workspace, geom, image, P, R, rotated}; return; }
+        ring[next++ % kPhaseNotes] = Note{workspace, geom, image, P, R, rotated};
     }
     // -> phase 1 ran on `workspace` with these arguments; the sums are consumed once
     bool consume(const void* workspace, const void* geom, const void* image, int P, int R)
@@ -359,6 +360,13 @@ public:
                 n = Note{};
                 return ok;
             }
+        return false;
+    }
+    // -> the phase 1 that last ran on `workspace` (and was not consumed yet) was called with sh_rotations
+    bool rotated(const void* workspace)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto& n : ring) if (n.workspace == workspace) return n.rotated;
         return false;
     }
 };
@@ -473,6 +481,8 @@ int validate_forward(const frg_forward_args& a)
         return fail(FRG_EINVAL, "shell_logits needs shell_cell_verts and shell_cells");
     if ((a.opacities == nullptr) == (a.raw_opacities == nullptr))
         return fail(FRG_EINVAL, "provide exactly one of opacities / raw_opacities");
+    if (a.sh_rotations && (!a.shs || a.colors_precomp))
+        return fail(FRG_EINVAL, "sh_rotations rotate the directions of the SH colour: they come with shs, not with colors_precomp");
     if ((a.shs == nullptr) == (a.colors_precomp == nullptr))
         return fail(FRG_EINVAL, "provide exactly one of shs / colors_precomp");
     if ((a.raw_scales == nullptr) != (a.raw_rotations == nullptr))
@@ -769,13 +779,14 @@ int forward_impl(const frg_forward_args& a)
     x.geom_chunk = a.geometry_alloc(a.user, frg_geometry_bytes(a.P));
     x.img_chunk = a.image_alloc(a.user, frg_image_bytes(a.width, a.height));
     if (!x.geom_chunk || !x.img_chunk) return fail(FRG_EALLOC, "allocation callback returned null");
-    g_fwd_notes.begin(x.geom_chunk, x.md.exact, x.md.fwd_only != 0);
+    g_fwd_notes.begin(x.geom_chunk, x.md.exact, x.md.fwd_only != 0, a.sh_rotations != nullptr);
     x.g = frg::GeomState::carve(x.geom_chunk, a.P);
     x.img = frg::ImageState::carve(x.img_chunk, a.width, a.height, g_global_bins.load() != 0);
     x.radii = a.radii ? a.radii : x.g.internal_radii;   // rasterizer_impl.cu:228-231
     x.in = frg::FwdInputs{a.means3D, a.scales, a.rotations, a.opacities, a.shs, a.cov3D_precomp, a.colors_precomp, a.viewmatrix, a.projmatrix, a.cam_pos};
     x.in.keep_mask = a.keep_mask;
     x.in.raw = raw_inputs_of(a);
+    x.in.sh_rotations = a.sh_rotations;
     x.sh.arm((a.shs != nullptr && !a.shell_logits) ? x.md.async_sh : 0);
     return a.instance_capacity > 0 ? forward_deferred(x) : forward_blocking(x);
 }
@@ -810,6 +821,11 @@ int validate_backward(const frg_backward_args& a)
     if (a.shell_logits && (!a.shell_cell_verts || !a.shell_cells || !a.dL_dshell_logits))
         return fail(FRG_EINVAL, "shell_logits needs shell_cell_verts, shell_cells and dL_dshell_logits");
     if (!a.dL_dmean2D || !a.dL_dopacity || !a.dL_dmean3D) return fail(FRG_EINVAL, "null gradient output");
+    if (a.sh_rotations && (!a.shs || a.colors_precomp))
+        return fail(FRG_EINVAL, "sh_rotations rotate the directions of the SH colour: they come with shs, not with colors_precomp");
+    // (dL_dsh == NULL asks for the factor of the SH gradient, which frg_sh_grad_from_views multiplies with the basis at the UNROTATED direction)
+    if (a.sh_rotations && !a.dL_dsh)
+        return fail(FRG_EINVAL, "sh_rotations with dL_dsh == NULL: rotated SH directions are a single-view render feature, the factored exchange does not carry them");
     // intermediates of the chain may be left out when the caller has no use for them: dL_dcolor when the SH rows are
     // written (it is then only the factor of dL_dsh), dL_dcov3D when the covariance comes from scales / rotations
     if (!a.dL_dcolor && !(a.shs && a.dL_dsh)) return fail(FRG_EINVAL, "dL_dcolor may only be NULL when shs and dL_dsh are given");
@@ -837,11 +853,20 @@ int validate_backward(const frg_backward_args& a)
 //     stamp back, one blocking copy of the forward's counters, which also tells the arithmetic.
 //   * R: a note that says the forward rendered MORE instances than this call's R (slots and item lists would overrun) is
 //     checked against the stamped count the same way before the call is refused.
+//   * sh_rotations: a note that says "rotated" where the call has no matrices, or the reverse, is checked against the stamp
+//     (FRG_FWD_ROTATED) the same way; behind a note that agrees -- possibly a stale one -- preprocess_bwd_kernel compares the
+//     stamp with its ROT instantiation and writes zero rows on a mismatch instead of gradients of the wrong directions.
 // -> *exact: 1 | 0 as stated or stamped, -1 "as stamped, on the device"
 int settle_forward_stamp(const frg_backward_args& a, const std::optional<FwdNote>& note, int* exact)
 {
     *exact = a.exact_blend == 0 ? -1 : FwdModes::pick(a.exact_blend, 1, 0);
-    const bool ask_the_stamp = !note || note->fwd_only || (note->rendered >= 0 && a.R < note->rendered);
+    // rotated SH directions (frg_forward_args::sh_rotations): the backward's matrices must be there exactly when the forward's
+    // were.  A note that disagrees with the call is a reason to read the stamp, and only the stamp refuses; a note that agrees
+    // lets the call through, and the per-Gaussian backward compares the stamp's bit with its own instantiation on the device
+    const bool rotated = a.sh_rotations != nullptr;
+    const char* const rot_missing = "the forward that filled these buffers was given sh_rotations: the backward needs the same matrices (frg_backward_args::sh_rotations is NULL)";
+    const char* const rot_extra = "sh_rotations given, but the forward that filled these buffers had none";
+    const bool ask_the_stamp = !note || note->fwd_only || (note->rendered >= 0 && a.R < note->rendered) || note->rotated != rotated;
     if (!ask_the_stamp || a.phase == 2) return FRG_OK;
     hipStream_t stream = (hipStream_t)a.hip_stream;
     frg::Counters* host = pinned_counters();
@@ -856,6 +881,7 @@ int settle_forward_stamp(const frg_backward_args& a, const std::optional<FwdNote
         return fail(FRG_EINVAL, "the forward that filled these buffers was called with forward_only = 1: it kept nothing for a backward");
     if ((uint32_t)a.R < host->num_rendered)
         return fail(FRG_EINVAL, "R = %d, but the forward that filled this geometry buffer rendered %u instances", a.R, host->num_rendered);
+    if (((flags & FRG_FWD_ROTATED) != 0u) != rotated) return fail(FRG_EINVAL, "%s", rotated ? rot_extra : rot_missing);
     if (*exact < 0) *exact = (flags & FRG_FWD_EXACT) ? 1 : 0;
     return FRG_OK;
 }
@@ -907,6 +933,7 @@ int backward_impl(const frg_backward_args& a)
 
     frg::FwdInputs in{a.means3D, a.scales, a.rotations, nullptr, a.shs, a.cov3D_precomp, a.colors_precomp, a.viewmatrix, a.projmatrix, a.campos};
     in.raw = raw_inputs_of(a);
+    in.sh_rotations = a.sh_rotations;
     frg::BwdOutputs out{a.dL_dmean2D, a.dL_dconic, a.dL_dopacity, a.dL_dcolor, a.dL_dmean3D, a.dL_dcov3D, a.dL_dsh, a.dL_dscale, a.dL_drot};
     out.dL_dshell_logits = a.dL_dshell_logits;
     out.dL_dshell_verts = a.dL_dshell_cell_verts;
@@ -925,7 +952,7 @@ int backward_impl(const frg_backward_args& a)
         FRG_STAGE(preprocess_bwd(pbw_flags | FRG_PBW_NO_HEAVY_LAUNCH, false, stream), "preprocess_bwd (phase 2)");
         return FRG_OK;
     }
-    if (phase == 1) g_phase_notes.record(a.workspace, a.geom_buffer, a.image_buffer, P, R);
+    if (phase == 1) g_phase_notes.record(a.workspace, a.geom_buffer, a.image_buffer, P, R, a.sh_rotations != nullptr);
     const bool ranged = a.range_count > 0;
     if (ranged) {
         if (phase != 1) return fail(FRG_EINVAL, "frg_backward_args: a range is offered with phase 1 only (phase %d)", phase);
@@ -962,6 +989,17 @@ int backward_impl(const frg_backward_args& a)
 }
 
 }  // namespace
+
+// The exchange entry points (api_ops.hip) run the per-Gaussian chain without the matrices and refuse a rotated forward early.
+// frg_pack_sum_rows asks what the phase 1 that filled its workspace was CALLED with (that call's matrices were checked against
+// the stamp); frg_sh_color_grad has only the geometry buffer, hence only the forward's note: an early refusal for the caller
+// that renders with rotations and trains view-parallel on the same buffers, no guarantee for copies of them.
+bool frg::forward_was_rotated(const void* geom_buffer)
+{
+    const std::optional<FwdNote> note = g_fwd_notes.find(geom_buffer);
+    return note && note->rotated;
+}
+bool frg::phase1_was_rotated(const void* workspace) { return g_phase_notes.rotated(workspace); }
 
 extern "C" {
 
@@ -1084,14 +1122,14 @@ int frg_forward_deferred(frg_alloc_fn geometry_alloc, frg_alloc_fn binning_alloc
 
 int frg_forward_ex(const frg_forward_args* a)
 {
-    // four generations of the struct: up to keep_mask (version 1 callers), with the raw-parameter fields, with the
-    // per-call modes, with forward_only
+    // five generations of the struct: up to keep_mask (version 1 callers), with the raw-parameter fields, with the
+    // per-call modes, with forward_only, with sh_rotations
     const size_t v1 = offsetof(frg_forward_args, raw_opacities), v2 = offsetof(frg_forward_args, exact_blend),
-                 v3 = offsetof(frg_forward_args, forward_only);
+                 v3 = offsetof(frg_forward_args, forward_only), v4 = offsetof(frg_forward_args, sh_rotations);
     frg_forward_args full;
-    if (!widen(a, {sizeof(frg_forward_args), v3, v2, v1}, &full))
-        return fail(FRG_EINVAL, "frg_forward_args: struct_size %zu, this library expects %zu (or %zu, %zu, %zu)", a ? a->struct_size : (size_t)0,
-                    sizeof(frg_forward_args), v3, v2, v1);
+    if (!widen(a, {sizeof(frg_forward_args), v4, v3, v2, v1}, &full))
+        return fail(FRG_EINVAL, "frg_forward_args: struct_size %zu, this library expects %zu (or %zu, %zu, %zu, %zu)", a ? a->struct_size : (size_t)0,
+                    sizeof(frg_forward_args), v4, v3, v2, v1);
     return forward_impl(full);
 }
 
@@ -1134,13 +1172,14 @@ int frg_backward(int P, int D, int M, int R, const float* background, int width,
 
 int frg_backward_ex(const frg_backward_args* a)
 {
-    // five generations of the struct: up to shell_*, + exact_blend / shell_bary_mode, + phase, + row_live, + range_first / range_count
+    // six generations of the struct: up to shell_*, + exact_blend / shell_bary_mode, + phase, + row_live, + range_first / range_count,
+    // + sh_rotations
     const size_t b1 = offsetof(frg_backward_args, exact_blend), b2 = offsetof(frg_backward_args, phase), b3 = offsetof(frg_backward_args, row_live),
-                 b4 = offsetof(frg_backward_args, range_first);
+                 b4 = offsetof(frg_backward_args, range_first), b5 = offsetof(frg_backward_args, sh_rotations);
     frg_backward_args full;
-    if (!widen(a, {sizeof(frg_backward_args), b4, b3, b2, b1}, &full))
-        return fail(FRG_EINVAL, "frg_backward_args: struct_size %zu, this library expects %zu (or %zu, %zu, %zu, %zu)", a ? a->struct_size : (size_t)0,
-                    sizeof(frg_backward_args), b4, b3, b2, b1);
+    if (!widen(a, {sizeof(frg_backward_args), b5, b4, b3, b2, b1}, &full))
+        return fail(FRG_EINVAL, "frg_backward_args: struct_size %zu, this library expects %zu (or %zu, %zu, %zu, %zu, %zu)", a ? a->struct_size : (size_t)0,
+                    sizeof(frg_backward_args), b5, b4, b3, b2, b1);
     return backward_impl(full);
 }
 

@@ -1,7 +1,8 @@
 // C ABI of libfrosting_rasterizer.so, everything beside the rasterizer (api.hip): the two gradient-exchange plans' pack,
 // scatter and combine calls, the fused Adam step, the photometric loss, the parameter activations, kNN, the shell
 // parameterisation and adaptive density control.  Each entry point validates its arguments and enqueues its kernels on
-// the caller's HIP stream; none keeps state between calls.
+// the caller's HIP stream; none keeps state between calls (the two that take a forward's buffers ask api.hip's notes whether
+// that forward rotated its SH directions, and refuse).
 #include "host_common.h"
 
 #include <cmath>
@@ -16,6 +17,7 @@ int frg_sh_color_grad(int P, const char* geom_buffer, const int* radii, const fl
     if (P < 0) return fail(FRG_EINVAL, "P < 0");
     if (P == 0) return FRG_OK;
     if (!geom_buffer || !radii || !dL_dcolors || !out_drgb) return fail(FRG_EINVAL, "null pointer");
+    if (frg::forward_was_rotated(geom_buffer)) return fail(FRG_EINVAL, "frg_sh_color_grad: %s", frg::kRotatedSingleView);
     const frg::GeomState g = frg::GeomState::carve(const_cast<char*>(geom_buffer), P);
     FRG_HIP(frg::launch_sh_color_grad(P, g, radii, dL_dcolors, out_drgb, (hipStream_t)hip_stream));
     return FRG_OK;
@@ -74,6 +76,7 @@ int frg_pack_sum_rows(int P, int R, int first, int count, char* workspace, size_
         return fail(FRG_EINVAL, "bad range: P=%d first=%d (a multiple of 64) count=%d", P, first, count);
     if (capacity_rows < 0 || capacity_rows > 0x7fffffffLL) return fail(FRG_EINVAL, "capacity_rows %lld", capacity_rows);
     if (!workspace || workspace_bytes < frg_backward_workspace_bytes(P, R)) return fail(FRG_EALLOC, "not the workspace of a backward with P=%d R=%d", P, R);
+    if (frg::phase1_was_rotated(workspace)) return fail(FRG_EINVAL, "frg_pack_sum_rows: %s", frg::kRotatedSingleView);
     if (!packet || packet_bytes < frg_sum_packet_bytes(count, capacity_rows) || reinterpret_cast<uintptr_t>(packet) % 16 != 0)
         return fail(FRG_EALLOC, "packet: need %zu bytes, 16-byte aligned", frg_sum_packet_bytes(count, capacity_rows));
     if (!drgb_masked || !viewmatrix || !projmatrix || !campos) return fail(FRG_EINVAL, "null pointer");

@@ -146,7 +146,8 @@ blend_fwd_kernel(int T, int gx, int W, int H, const uint2* __restrict__ ranges,
     __syncthreads();                   // the only workgroup barrier of the kernel: the four waves start together anyway
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         counters->bwd_seg_log = (uint32_t)seg_log;
-        counters->fwd_flags = FRG_FWD_STAMPED | (EXACT ? FRG_FWD_EXACT : 0u) | (ckpt ? 0u : FRG_FWD_ONLY);
+        // (FRG_FWD_ROTATED: left by this forward's preprocess_fwd_kernel, which knows about sh_rotations)
+        counters->fwd_flags = FRG_FWD_STAMPED | (EXACT ? FRG_FWD_EXACT : 0u) | (ckpt ? 0u : FRG_FWD_ONLY) | (counters->fwd_flags & FRG_FWD_ROTATED);
     }
     int tile;
     if (class_tiles) {

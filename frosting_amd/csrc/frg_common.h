@@ -144,6 +144,7 @@ struct Counters {            // written by the forward's kernels; 56 bytes, post
 };
 #define FRG_FWD_EXACT 1u
 #define FRG_FWD_ONLY 2u
+#define FRG_FWD_ROTATED 4u       // frg_forward_args::sh_rotations was given: the SH directions (and sh_dir) are those of d @ R
 #define FRG_FWD_STAMPED 0x80000000u
 static_assert(sizeof(Counters) == 56, "Counters: 14 words (the mailbox's second line is 8 + 56 bytes)");
 // Pinned HOST memory the scan workgroups write with system-scope stores, polled by the forward's host thread: the

@@ -123,6 +123,21 @@ __device__ __forceinline__ int sh_weights(int deg, float x, float y, float z, fl
     return 16;
 }
 
+// Per-Gaussian rotation of the SH view direction (frg_forward_args::sh_rotations; the reference's edited / animated
+// scenes, frosting_model.py:1482): d' = d @ R, R = Gaussian idx's row-major 3x3, used AS GIVEN -- neither
+// orthonormalised nor d' renormalised.  Left to right, no contraction: the reference's batched product in float32.
+__device__ __forceinline__ float3 sh_rotate_dir(const float* __restrict__ sh_rot, int idx, float x, float y, float z)
+{
+    const float* R = sh_rot + 9 * (size_t)idx;
+    return make_float3(x * R[0] + y * R[3] + z * R[6], x * R[1] + y * R[4] + z * R[7], x * R[2] + y * R[5] + z * R[8]);
+}
+// ... and its transpose for the backward: dL/dd = R . dL/dd'
+__device__ __forceinline__ float3 sh_rotate_back(const float* __restrict__ sh_rot, int idx, float gx, float gy, float gz)
+{
+    const float* R = sh_rot + 9 * (size_t)idx;
+    return make_float3(R[0] * gx + R[1] * gy + R[2] * gz, R[3] * gx + R[4] * gy + R[5] * gz, R[6] * gx + R[7] * gy + R[8] * gz);
+}
+
 // d(colour_ch)/d(dir): the share of one coefficient (basis i, value sv of the channel) in
 //   ddx = sum_i dbasis_i/dx * sh[i][ch], ddy, ddz                       (backward.cu:47-137).
 // Evaluated by the FORWARD while the coefficients pass through LDS anyway, and stored (9 floats per Gaussian,

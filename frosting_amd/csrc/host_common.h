@@ -10,6 +10,14 @@ namespace frg {
 // -> code, so that a failing entry point can `return fail(FRG_EINVAL, "...")`.
 int fail(int code, const char* fmt, ...);
 
+// What api.hip remembers of the forwards (its notes), for the exchange entry points of api_ops.hip: was the forward that last
+// filled this geometry buffer / whose backward's phase 1 last ran on this workspace given sh_rotations?  Those entry points run
+// the per-Gaussian chain without the matrices and refuse such buffers (kRotatedSingleView).
+bool forward_was_rotated(const void* geom_buffer);
+bool phase1_was_rotated(const void* workspace);
+constexpr const char* kRotatedSingleView = "the forward that filled these buffers was given sh_rotations: rotated SH directions are a "
+                                           "single-view render feature, the view-parallel exchanges do not carry them";
+
 // spin-wait hint of the mailbox polls (the host side is not tied to x86)
 inline void cpu_relax()
 {

@@ -63,6 +63,7 @@ struct FwdInputs {
     const float *viewmatrix, *projmatrix, *cam_pos;
     const unsigned char* keep_mask = nullptr;   // optional per-Gaussian skip flag (0 = not in this view)
     RawInputs raw;                              // optional: the model's raw parameters instead of activated tensors
+    const float* sh_rotations = nullptr;        // optional [P,3,3] (with shs): the SH view direction of Gaussian i is d @ R_i (gauss_math.h sh_rotate_dir)
 };
 
 // defer_sh: the SH colours are left to launch_sh_color (any stream ordered after this launch, before the blend)

@@ -73,6 +73,7 @@ preprocess_one(int idx, const ViewParams& vp, const ViewMats& vmx,
                const float* __restrict__ rotations, const float* __restrict__ opacities,
                const float* __restrict__ shs, const float* __restrict__ cov3D_precomp,
                const float* __restrict__ colors_precomp, const unsigned char* __restrict__ keep_mask, const RawInputs& raw,
+               const float* __restrict__ sh_rot,
                float4* rec /* this Gaussian's record: [0] xydr, [1] conic + opacity */,
                Counters* __restrict__ counters, int prefiltered, int& radius_i, int& x0, int& y0, int& x1, int& y1,
                float3& dir, float& depth)
@@ -120,6 +121,7 @@ preprocess_one(int idx, const ViewParams& vp, const ViewMats& vmx,
         float dx = p.x - vmx.campos[0], dy = p.y - vmx.campos[1], dz = p.z - vmx.campos[2];
         const float len = sqrtf(dx * dx + dy * dy + dz * dz);
         dir = make_float3(dx / len, dy / len, dz / len);
+        if (sh_rot) dir = sh_rotate_dir(sh_rot, idx, dir.x, dir.y, dir.z);   // 36 bytes, read by the Gaussians that survived culling only
     }
     return touched;
 }
@@ -363,7 +365,7 @@ preprocess_fwd_kernel(int P, ViewParams vp, const float* __restrict__ viewmatrix
                       uint32_t* __restrict__ bin_matrix, uint32_t* __restrict__ tile_count,
                       uint32_t* __restrict__ block_sums, Counters* __restrict__ counters, int prefiltered,
                       uint32_t* __restrict__ row_matrix, int band_w, int nbands, float* __restrict__ sh_dir,
-                      uint32_t* __restrict__ heavy_waves, uint32_t* __restrict__ sh_layout)
+                      uint32_t* __restrict__ heavy_waves, uint32_t* __restrict__ sh_layout, const float* __restrict__ sh_rot)
 {
     constexpr bool SH16 = SHMODE == SH_STREAM || SHMODE == SH_STREAM_SPARSE;
     constexpr bool TIGHT = BINMODE == BIN_TIGHT, CELLS = BINMODE == BIN_CELLS;
@@ -390,6 +392,7 @@ preprocess_fwd_kernel(int P, ViewParams vp, const float* __restrict__ viewmatrix
         for (int t = threadIdx.x; t < nbins; t += FRG_BIN_THREADS) lds_bins[t] = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         heavy_waves[0] = 0;   // (filled where point_offsets is finished)
+        counters->fwd_flags = sh_rot ? FRG_FWD_ROTATED : 0u;   // the blend's stamp keeps this bit (blend_impl.h)
         // bit 0: sh_dir rows by rank in sparsely visible waves; bit 1: no sh_dir rows at all (only the float4-streamed pass has that form)
         if (SHMODE != SH_DEFER) *sh_layout = (SHMODE == SH_STREAM_SPARSE ? 1u : 0u) | ((vp.sh_no_dir && SHMODE != SH_INLINE) ? 2u : 0u);    // (SH_DEFER: sh_color_kernel says)
     }
@@ -408,7 +411,7 @@ preprocess_fwd_kernel(int P, ViewParams vp, const float* __restrict__ viewmatrix
             int radius_i, x0, y0, x1, y1;
             float depth = 0.f;
             touched = preprocess_one(idx, vp, vmx, means3D, scales, rotations, opacities, shs, cov3D_precomp,
-                                     colors_precomp, keep_mask, raw, rec, counters, prefiltered,
+                                     colors_precomp, keep_mask, raw, sh_rot, rec, counters, prefiltered,
                                      radius_i, x0, y0, x1, y1, dir, depth);
             radii[idx] = radius_i;
             tiles_touched[idx] = touched;
@@ -509,7 +512,7 @@ template <bool SH16, bool SPARSE>
 __global__ void __launch_bounds__(SHC_THREADS)
 sh_color_kernel(int P, int D, int M, const float* __restrict__ cam_pos, const float* __restrict__ means3D,
                 const int* __restrict__ radii, const float* __restrict__ shs, float4* __restrict__ rgb_clamped,
-                float* __restrict__ sh_dir, uint32_t* __restrict__ sh_layout, int sh_no_dir)
+                float* __restrict__ sh_dir, uint32_t* __restrict__ sh_layout, int sh_no_dir, const float* __restrict__ sh_rot)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) *sh_layout = ((SH16 && SPARSE) ? 1u : 0u) | ((SH16 && sh_no_dir) ? 2u : 0u);
     __shared__ float4 sh_lds[SH16 ? (SHC_THREADS / 64) * PRE_SUB * PRE_ROW_F4 : 1];
@@ -526,6 +529,7 @@ sh_color_kernel(int P, int D, int M, const float* __restrict__ cam_pos, const fl
         float dx = p.x - cx, dy = p.y - cy, dz = p.z - cz;
         const float len = sqrtf(dx * dx + dy * dy + dz * dz);
         dir = make_float3(dx / len, dy / len, dz / len);
+        if (sh_rot) dir = sh_rotate_dir(sh_rot, idx, dir.x, dir.y, dir.z);
     }
     if (SH16) {
         const float4 col = sh_stream_wave<SPARSE>(D, reinterpret_cast<const float4*>(shs) + (size_t)idx0 * 12, min(64, P - idx0), touched, dir,
@@ -1140,7 +1144,7 @@ static hipError_t launch_pre_variant(int P, const ViewParams& vp, const FwdInput
                        in.projmatrix, in.cam_pos, in.means3D, in.scales, in.rotations, in.opacities, in.shs,
                        in.cov3D_precomp, in.colors_precomp, in.keep_mask, in.raw, radii, g.xydr, g.conic_opacity, g.rgb_clamped,
                        g.tiles_touched, g.depth_rect, img.bin_matrix, img.tile_count, g.block_sums, img.counters, prefiltered,
-                       BINMODE == BIN_CELLS ? img.row_matrix : nullptr, img.band_w, img.nbands, g.sh_dir, g.heavy_waves, g.sh_layout);
+                       BINMODE == BIN_CELLS ? img.row_matrix : nullptr, img.band_w, img.nbands, g.sh_dir, g.heavy_waves, g.sh_layout, in.sh_rotations);
     return hipGetLastError();
 }
 
@@ -1171,11 +1175,11 @@ hipError_t launch_sh_color(int P, const ViewParams& vp, const FwdInputs& in, con
     const dim3 grid((P + SHC_THREADS - 1) / SHC_THREADS), block(SHC_THREADS);
     if (sh_streamable(in, vp)) {
         if (vp.sparse_sh)
-            hipLaunchKernelGGL((sh_color_kernel<true, true>), grid, block, 0, s, P, vp.D, vp.M, in.cam_pos, in.means3D, radii, in.shs, g.rgb_clamped, g.sh_dir, g.sh_layout, vp.sh_no_dir);
+            hipLaunchKernelGGL((sh_color_kernel<true, true>), grid, block, 0, s, P, vp.D, vp.M, in.cam_pos, in.means3D, radii, in.shs, g.rgb_clamped, g.sh_dir, g.sh_layout, vp.sh_no_dir, in.sh_rotations);
         else
-            hipLaunchKernelGGL((sh_color_kernel<true, false>), grid, block, 0, s, P, vp.D, vp.M, in.cam_pos, in.means3D, radii, in.shs, g.rgb_clamped, g.sh_dir, g.sh_layout, vp.sh_no_dir);
+            hipLaunchKernelGGL((sh_color_kernel<true, false>), grid, block, 0, s, P, vp.D, vp.M, in.cam_pos, in.means3D, radii, in.shs, g.rgb_clamped, g.sh_dir, g.sh_layout, vp.sh_no_dir, in.sh_rotations);
     } else
-        hipLaunchKernelGGL((sh_color_kernel<false, false>), grid, block, 0, s, P, vp.D, vp.M, in.cam_pos, in.means3D, radii, in.shs, g.rgb_clamped, g.sh_dir, g.sh_layout, vp.sh_no_dir);
+        hipLaunchKernelGGL((sh_color_kernel<false, false>), grid, block, 0, s, P, vp.D, vp.M, in.cam_pos, in.means3D, radii, in.shs, g.rgb_clamped, g.sh_dir, g.sh_layout, vp.sh_no_dir, in.sh_rotations);
     return hipGetLastError();
 }
 

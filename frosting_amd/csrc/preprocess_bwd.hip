@@ -46,7 +46,10 @@ __device__ __forceinline__ void wave_fence()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <bool SH16, bool HEAVY>
+// ROT: the forward's SH directions were rotated (frg_backward_args::sh_rotations).  A template parameter, not a wave-uniform
+// branch: with the branch the plain SH16 kernel went from 94 to 100 VGPRs, from five waves per SIMD to four
+// (profiles/r07_sh_rotations_resources.txt); the instantiations without it are the code they were.
+template <bool SH16, bool HEAVY, bool ROT>
 __global__ void __launch_bounds__(HEAVY ? BWD_HEAVY_WAVES * 64 : BWD_THREADS, 4)
 preprocess_bwd_kernel(int P, ViewParams vp, const float* __restrict__ viewmatrix,
                       const float* __restrict__ projmatrix, const float* __restrict__ cam_pos,
@@ -63,8 +66,10 @@ preprocess_bwd_kernel(int P, ViewParams vp, const float* __restrict__ viewmatrix
                       RawInputs raw, float* __restrict__ dL_dshell_logits, float* __restrict__ dL_dshell_verts,
                       const float* __restrict__ sh_dir, int flags, const uint32_t* __restrict__ heavy,
                       const uint32_t* __restrict__ sh_layout, float* __restrict__ sums, unsigned char* __restrict__ row_live,
-                      unsigned long long* __restrict__ live_masks, float* __restrict__ view_dir_terms, int first_block)
+                      unsigned long long* __restrict__ live_masks, float* __restrict__ view_dir_terms, int first_block,
+                      const float* __restrict__ sh_rotations /* frg_backward_args::sh_rotations: the forward's SH directions were d @ R */)
 {
+    const float* __restrict__ const sh_rot = ROT ? sh_rotations : nullptr;
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[(HEAVY ? BWD_HEAVY_WAVES : BWD_THREADS / 64) * BWD_LDS_WORDS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t* lds = lds_all + wave * BWD_LDS_WORDS;
@@ -142,7 +147,11 @@ preprocess_bwd_kernel(int P, ViewParams vp, const float* __restrict__ viewmatrix
     uint16_t* live = reinterpret_cast<uint16_t*>(shbuf + 96);           // [BWD_WIN] behind own_co / own_xy
     if (ablate & 1) S = 0;   // TIMING EXPERIMENT ONLY (frg_set_option("ablate")): no slot reduction
     if (flags & FRG_PBW_FROM_SUMS) S = 0;   // phase 2 of a two-call backward: the sums were left by phase 1
-    if (counters->fwd_flags & FRG_FWD_ONLY) S = 0;   // the forward kept nothing for a backward (and the blend backward wrote no slot): zero rows
+    // ... or the forward's SH directions are not this instantiation's (a host whose note of the forward was stale let the call through,
+    // api.hip settle_forward_stamp): zero rows instead of gradients of the wrong directions
+    const uint32_t fwd_flags = counters->fwd_flags;
+    const bool fwd_usable = !(fwd_flags & FRG_FWD_ONLY) && ((fwd_flags & FRG_FWD_ROTATED) != 0u) == ROT;
+    if (!fwd_usable) S = 0;   // the forward kept nothing for a backward (and the blend backward wrote no slot): zero rows
     const uint32_t nwin = (S + BWD_WIN - 1) / BWD_WIN;                   // wave-uniform
     // on the forward's list: the 16-wave launch has it -- unless the host skipped that launch (FRG_PBW_NO_HEAVY_LAUNCH:
     // its forward posted "no such wave"), in which case a wave that does own that many slots is reduced right here,
@@ -299,7 +308,7 @@ preprocess_bwd_kernel(int P, ViewParams vp, const float* __restrict__ viewmatrix
                     const float3 mm = param_mean(means3D, raw, idx);
                     const float dox = mm.x - vmx.campos[0], doy = mm.y - vmx.campos[1], doz = mm.z - vmx.campos[2];
                     const float len = sqrtf(dox * dox + doy * doy + doz * doz);
-                    const ShDir sd(vp.D, dox / len, doy / len, doz / len);
+                    const ShDir sd(vp.D, dox / len, doy / len, doz / len);    // (never with sh_rotations: frg_pack_sum_rows, the one reader of these terms, refuses)
                     const int ncoef = (vp.D + 1) * (vp.D + 1);
                     const float4* row = reinterpret_cast<const float4*>(shs) + (size_t)idx * 12;
 #pragma unroll
@@ -338,7 +347,7 @@ preprocess_bwd_kernel(int P, ViewParams vp, const float* __restrict__ viewmatrix
     }
     if (flags & FRG_PBW_FROM_SUMS) {
 #pragma unroll
-        for (int c = 0; c < FRG_SLOT_FLOATS; c++) part[c] = valid ? sums[(size_t)idx * FRG_SLOT_FLOATS + c] : 0.0f;
+        for (int c = 0; c < FRG_SLOT_FLOATS; c++) part[c] = (valid && fwd_usable) ? sums[(size_t)idx * FRG_SLOT_FLOATS + c] : 0.0f;
     }
     // LIVE Gaussians: those whose slot sums are not all zero.  At C3 only one visible Gaussian in seven is reached by
     // a pixel before its tiles saturate (370 000 of 2.5 M); for the others every term below is a product with these
@@ -368,7 +377,9 @@ preprocess_bwd_kernel(int P, ViewParams vp, const float* __restrict__ viewmatrix
         const float3 m = param_mean(means3D, raw, idx);
         const float dox = m.x - vmx.campos[0], doy = m.y - vmx.campos[1], doz = m.z - vmx.campos[2];   // the expressions of section 4 (and of the forward)
         const float len = sqrtf(dox * dox + doy * doy + doz * doz);
-        const ShDir sd(vp.D, dox / len, doy / len, doz / len);
+        float3 dv = make_float3(dox / len, doy / len, doz / len);
+        if (sh_rot) dv = sh_rotate_dir(sh_rot, idx, dv.x, dv.y, dv.z);      // sh_dir is d colour / d d', evaluated at d'
+        const ShDir sd(vp.D, dv.x, dv.y, dv.z);
         const int ncoef = (vp.D + 1) * (vp.D + 1);
         const float4* row = reinterpret_cast<const float4*>(shs) + (size_t)idx * 12;
 #pragma unroll
@@ -493,6 +504,7 @@ preprocess_bwd_kernel(int P, ViewParams vp, const float* __restrict__ viewmatrix
             dox = mean.x - vmx.campos[0]; doy = mean.y - vmx.campos[1]; doz = mean.z - vmx.campos[2];
             const float len = sqrtf(dox * dox + doy * doy + doz * doz);
             x = dox / len; y = doy / len; z = doz / len;
+            if (sh_rot) { const float3 dv = sh_rotate_dir(sh_rot, idx, x, y, z); x = dv.x; y = dv.y; z = dv.z; }    // the basis at d' (the forward's)
 #pragma unroll
             for (int ch = 0; ch < 3; ch++) dRGB[ch] = part[ch] * (((clamp_bits >> ch) & 1u) ? 0.f : 1.f);
         }
@@ -513,9 +525,11 @@ preprocess_bwd_kernel(int P, ViewParams vp, const float* __restrict__ viewmatrix
             }
         }
         if (has_grad) {
-            const float dd0 = shd[0] * dRGB[0] + shd[1] * dRGB[1] + shd[2] * dRGB[2];
-            const float dd1 = shd[3] * dRGB[0] + shd[4] * dRGB[1] + shd[5] * dRGB[2];
-            const float dd2 = shd[6] * dRGB[0] + shd[7] * dRGB[1] + shd[8] * dRGB[2];
+            float dd0 = shd[0] * dRGB[0] + shd[1] * dRGB[1] + shd[2] * dRGB[2];
+            float dd1 = shd[3] * dRGB[0] + shd[4] * dRGB[1] + shd[5] * dRGB[2];
+            float dd2 = shd[6] * dRGB[0] + shd[7] * dRGB[1] + shd[8] * dRGB[2];
+            // these are dL/dd'; d' = d @ R, so dL/dd = R . dL/dd' -- and dnormvdv below is that of the UNROTATED offset
+            if (sh_rot) { const float3 gd = sh_rotate_back(sh_rot, idx, dd0, dd1, dd2); dd0 = gd.x; dd1 = gd.y; dd2 = gd.z; }
             // auxiliary.h:107-117 dnormvdv
             const float sum2 = dox * dox + doy * doy + doz * doz;
             const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
@@ -673,17 +687,19 @@ hipError_t launch_preprocess_bwd(int P, const ViewParams& vp, const FwdInputs& i
     // float4-streamed SH needs the reference's usual layout: 16 coefficients, 16-byte aligned rows
     const bool sh16 = in.shs && vp.M == 16 && (reinterpret_cast<uintptr_t>(in.shs) % 16 == 0) &&
                       (reinterpret_cast<uintptr_t>(o.dL_dsh) % 16 == 0);
-#define FRG_PBW(S16, HV, GRID, BLOCK)                                                                                  \
-    hipLaunchKernelGGL((preprocess_bwd_kernel<S16, HV>), GRID, BLOCK, 0, s, P, vp, in.viewmatrix, in.projmatrix,              \
+#define FRG_PBW_ROT(S16, HV, ROT, GRID, BLOCK)                                                                         \
+    hipLaunchKernelGGL((preprocess_bwd_kernel<S16, HV, ROT>), GRID, BLOCK, 0, s, P, vp, in.viewmatrix, in.projmatrix,         \
                        in.cam_pos, in.means3D, radii, in.shs, in.scales, in.rotations, in.cov3D_precomp, g.xydr,          \
                        g.rgb_clamped, g.conic_opacity, g.point_offsets, img.cutoff, img.counters, slots, o.dL_dmean2D,     \
                        o.dL_dconic, o.dL_dopacity, o.dL_dcolor, o.dL_dmean3D, o.dL_dcov3D, o.dL_dsh, o.dL_dscale, o.dL_drot, ablate,       \
-                       in.raw, o.dL_dshell_logits, o.dL_dshell_verts, g.sh_dir, flags, g.heavy_waves, g.sh_layout, sums, o.row_live, live_masks, view_dir_terms, first_block)
+                       in.raw, o.dL_dshell_logits, o.dL_dshell_verts, g.sh_dir, flags, g.heavy_waves, g.sh_layout, sums, o.row_live, live_masks, view_dir_terms, first_block, in.sh_rotations)
+#define FRG_PBW(S16, HV, GRID, BLOCK) do { if (in.sh_rotations) FRG_PBW_ROT(S16, HV, true, GRID, BLOCK); else FRG_PBW_ROT(S16, HV, false, GRID, BLOCK); } while (0)
     // the listed waves (usually none: the workgroups read the count and leave)
     const dim3 hgrid(256), hblock(BWD_HEAVY_WAVES * 64);
     if (heavy_only) { if (sh16) FRG_PBW(true, true, hgrid, hblock); else FRG_PBW(false, true, hgrid, hblock); }
     else { if (sh16) FRG_PBW(true, false, grid, block); else FRG_PBW(false, false, grid, block); }
 #undef FRG_PBW
+#undef FRG_PBW_ROT
     return hipGetLastError();
 }
 

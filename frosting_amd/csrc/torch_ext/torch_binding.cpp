@@ -67,6 +67,17 @@ const float* opt_f32(const torch::Tensor& t, const torch::Device& dev, const cha
     return keep_alive.data_ptr<float>();
 }
 
+// frg_forward_args / frg_backward_args::sh_rotations: [P,3,3] float32 on the Gaussians' device, made contiguous; an empty
+// tensor means none
+const float* opt_sh_rotations(const torch::Tensor& t, int P, const torch::Device& dev, torch::Tensor& keep_alive)
+{
+    if (!t.defined() || t.numel() == 0) return nullptr;
+    TORCH_CHECK(t.dim() == 3 && t.size(0) == P && t.size(1) == 3 && t.size(2) == 3 && t.scalar_type() == torch::kFloat32 && t.device() == dev,
+                "sh_rotations must be a float32 tensor of shape (num_points, 3, 3) on the Gaussians' device");
+    keep_alive = t.contiguous();
+    return keep_alive.data_ptr<float>();
+}
+
 void check_rc(int rc, const char* what)
 {
     TORCH_CHECK(rc >= 0, what, " failed (", rc, "): ", frg_last_error());
@@ -79,7 +90,7 @@ forward_common(const torch::Tensor& background, const torch::Tensor& means3D, co
                const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
                const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
                const bool prefiltered, const bool debug, const torch::Tensor* keep_mask, const bool forward_only = false,
-               const int exact_blend = -1)
+               const int exact_blend = -1, const torch::Tensor* sh_rotations = nullptr)
 {
     TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must have dimensions (num_points, 3)");  // rasterize_points.cu:57-59
     TORCH_CHECK(means3D.is_cuda(), "frosting_amd rasterizer: means3D must live on a ROCm device (no CPU path)");
@@ -92,7 +103,7 @@ forward_common(const torch::Tensor& background, const torch::Tensor& means3D, co
     torch::Tensor radii = torch::empty({P}, means3D.options().dtype(torch::kInt32));
     Chunks chunks(dev);
 
-    torch::Tensor k[12];
+    torch::Tensor k[13];
     frg_forward_args a{};
     a.struct_size = sizeof(a);
     a.geometry_alloc = &Chunks::grow_geom;
@@ -135,6 +146,7 @@ forward_common(const torch::Tensor& background, const torch::Tensor& means3D, co
         k[11] = keep_mask->contiguous();
         a.keep_mask = static_cast<const unsigned char*>(k[11].data_ptr());
     }
+    if (sh_rotations) a.sh_rotations = opt_sh_rotations(*sh_rotations, P, dev, k[12]);
     const int rendered = frg_forward_ex(&a);
     check_rc(rendered, "frg_forward");
     return std::make_tuple(rendered, out_color, radii, chunks.geom.t, chunks.binning.t, chunks.img.t);
@@ -194,7 +206,8 @@ backward_common(const torch::Tensor& background, const torch::Tensor& means3D, c
                 const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
                 const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree,
                 const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
-                const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const bool debug, const int exact_blend)
+                const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const bool debug, const int exact_blend,
+                const torch::Tensor* sh_rotations = nullptr)
 {
     TORCH_CHECK(exact_blend >= -1 && exact_blend <= 1, "exact_blend must be -1 (as the forward), 0 or 1");
     TORCH_CHECK(means3D.is_cuda(), "frosting_amd rasterizer: means3D must live on a ROCm device (no CPU path)");
@@ -216,7 +229,7 @@ backward_common(const torch::Tensor& background, const torch::Tensor& means3D, c
     torch::Tensor dL_drotations = has_sr ? torch::empty({P, 4}, f32) : torch::zeros({P, 4}, f32);
 
     if (P != 0) {
-        torch::Tensor k[11];
+        torch::Tensor k[12];
         const size_t ws_bytes = frg_backward_workspace_bytes(P, R);
         torch::Tensor workspace = torch::empty({static_cast<int64_t>(ws_bytes)}, torch::TensorOptions(torch::kByte).device(dev));
         torch::Tensor radii_c = radii.contiguous();
@@ -258,6 +271,7 @@ backward_common(const torch::Tensor& background, const torch::Tensor& means3D, c
         a.debug = debug ? 1 : 0;
         a.hip_stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
         a.exact_blend = exact_blend + 1;            // frg_backward_args: 0 = as the forward, k + 1 = value k
+        if (sh_rotations) a.sh_rotations = opt_sh_rotations(*sh_rotations, P, dev, k[11]);
         const int rc = frg_backward_ex(&a);
         check_rc(rc, "frg_backward");
         // `workspace` returns to the caching allocator here; reuse is ordered on this same stream
@@ -311,6 +325,38 @@ RasterizeGaussiansExHIP(const torch::Tensor& background, const torch::Tensor& me
     return forward_common(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                           projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug,
                           &keep_mask, forward_only, exact_blend);
+}
+
+// rasterize_gaussians_ex + sh_rotations ([P,3,3], or empty for none): the SH colour of Gaussian i is evaluated at d @ R_i
+std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+RasterizeGaussiansRotHIP(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
+                         const torch::Tensor& opacity, const torch::Tensor& scales, const torch::Tensor& rotations,
+                         const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+                         const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                         const int image_height, const int image_width, const torch::Tensor& sh, const int degree,
+                         const torch::Tensor& campos, const bool prefiltered, const bool debug,
+                         const torch::Tensor& keep_mask, const int exact_blend, const bool forward_only,
+                         const torch::Tensor& sh_rotations)
+{
+    return forward_common(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                          projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug,
+                          &keep_mask, forward_only, exact_blend, &sh_rotations);
+}
+
+// rasterize_gaussians_backward_ex + the forward's sh_rotations (empty exactly when it had none)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+RasterizeGaussiansBackwardRotHIP(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
+                                 const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
+                                 const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+                                 const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                                 const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree,
+                                 const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
+                                 const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const bool debug,
+                                 const int exact_blend, const torch::Tensor& sh_rotations)
+{
+    return backward_common(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                           projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
+                           imageBuffer, debug, exact_blend, &sh_rotations);
 }
 
 // DGR/rasterize_points.h:64-67, rasterize_points.cu:198-217
@@ -454,6 +500,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("rasterize_gaussians_forward_only", &RasterizeGaussiansForwardOnlyHIP);
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansExHIP);
     m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardExHIP);
+    m.def("rasterize_gaussians_rot", &RasterizeGaussiansRotHIP);
+    m.def("rasterize_gaussians_backward_rot", &RasterizeGaussiansBackwardRotHIP);
     m.def("densify_accumulate", &DensifyAccumulateHIP);
     m.def("densify_plan", &DensifyPlanHIP);
     m.def("densify_apply", &DensifyApplyHIP);

@@ -16,6 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .rasterizer import check_sh_rotations
 
 
 def _f32(t):
@@ -25,7 +26,7 @@ def _f32(t):
 class _RasterizeRaw(torch.autograd.Function):
     # tensor inputs, in the order of forward()'s arguments after `settings` and `opts`
     NAMES = ("shs", "raw_opacity", "raw_scale", "raw_rot", "means3D", "shell_logits", "shell_cell_verts", "shell_cells",
-             "keep_mask", "means2D")
+             "keep_mask", "means2D", "sh_rotations")
 
     @staticmethod
     def _views(tensors):
@@ -35,11 +36,12 @@ class _RasterizeRaw(torch.autograd.Function):
                     means=_f32(d["means3D"]), lg=_f32(d["shell_logits"]),
                     cv=None if d["shell_cell_verts"] is None else _f32(d["shell_cell_verts"]).reshape(-1, 6, 3),
                     ci=None if d["shell_cells"] is None else d["shell_cells"].to(torch.int64).contiguous(),
-                    mask=None if d["keep_mask"] is None else d["keep_mask"].contiguous())
+                    mask=None if d["keep_mask"] is None else d["keep_mask"].contiguous(),
+                    rot=d["sh_rotations"])
 
     @staticmethod
     def forward(ctx, settings, opts, shs, raw_opacity, raw_scale, raw_rot, means3D, shell_logits, shell_cell_verts, shell_cells,
-                keep_mask, means2D):
+                keep_mask, means2D, sh_rotations):
         L = _lib.lib()
         s = settings
         shelled = shell_logits is not None
@@ -48,7 +50,10 @@ class _RasterizeRaw(torch.autograd.Function):
         if dev.type != "cuda":
             raise RuntimeError("frosting_amd.fused: parameters must live on a ROCm device (no CPU path)")
         P, H, W = int(ref.shape[0]), int(s.image_height), int(s.image_width)
-        inputs = (shs, raw_opacity, raw_scale, raw_rot, means3D, shell_logits, shell_cell_verts, shell_cells, keep_mask, means2D)
+        if sh_rotations is not None:
+            sh_rotations = check_sh_rotations(sh_rotations, P, dev)
+        inputs = (shs, raw_opacity, raw_scale, raw_rot, means3D, shell_logits, shell_cell_verts, shell_cells, keep_mask, means2D,
+                  sh_rotations)
         t = _RasterizeRaw._views(inputs)
         cam = dict(bg=_f32(s.bg), view=_f32(s.viewmatrix), proj=_f32(s.projmatrix), campos=_f32(s.campos))
         modes = dict(opts.get("modes") or {})
@@ -66,7 +71,7 @@ class _RasterizeRaw(torch.autograd.Function):
                 tan_fovx=float(s.tanfovx), tan_fovy=float(s.tanfovy), prefiltered=int(bool(s.prefiltered)), out_color=color,
                 radii=radii, debug=int(bool(s.debug)), hip_stream=torch.cuda.current_stream(dev).cuda_stream, keep_mask=t["mask"],
                 raw_opacities=t["ro"], raw_scales=t["rs"], raw_rotations=t["rr"], shell_logits=t["lg"], shell_cell_verts=t["cv"],
-                shell_cells=t["ci"], shell_bary_mode=bary_mode, modes=modes)
+                shell_cells=t["ci"], shell_bary_mode=bary_mode, modes=modes, sh_rotations=t["rot"])
             R = _lib.check(L.frg_forward_ex(C.byref(a)), "frg_forward_ex")
         # the INPUT tensors are saved (autograd's version counters then catch an in-place optimizer step between this
         # forward and its backward); their float32 views are re-derived in backward -- free for contiguous float32
@@ -112,27 +117,31 @@ class _RasterizeRaw(torch.autograd.Function):
                     workspace=work, workspace_bytes=ws, debug=int(bool(s.debug)), hip_stream=torch.cuda.current_stream(dev).cuda_stream,
                     raw_opacities=t["ro"], raw_scales=t["rs"], raw_rotations=t["rr"], shell_logits=t["lg"], shell_cell_verts=t["cv"],
                     shell_cells=t["ci"], dL_dshell_logits=g["lg"], dL_dshell_cell_verts=g["cv"], exact_blend=ctx.exact,
-                    shell_bary_mode=ctx.bary_mode)
+                    shell_bary_mode=ctx.bary_mode, sh_rotations=t["rot"])
                 _lib.check(L.frg_backward_ex(C.byref(a)), "frg_backward_ex")
                 work.record_stream(torch.cuda.current_stream(dev))
         g_cv = None if out["cv"] is None else out["cv"].reshape(ctx.cv_shape)
         # settings, opts, shs, raw_opacity, raw_scale, raw_rot, means3D, shell_logits, shell_cell_verts, shell_cells, keep_mask,
-        # means2D (the reference's viewspace gradient: the densification statistics read it, gaussian_model.py:404-407)
+        # means2D (the reference's viewspace gradient: the densification statistics read it, gaussian_model.py:404-407),
+        # sh_rotations (no gradient)
         return (None, None, out["sh"], out["op"].reshape(ctx.ro_shape), out["sc"], out["rot"],
-                None if shelled else out["m3"], out["lg"], g_cv, None, None, out["m2"] if ctx.present[9] else None)
+                None if shelled else out["m3"], out["lg"], g_cv, None, None, out["m2"] if ctx.present[9] else None, None)
 
 
 def rasterize_raw(settings, shs, raw_opacity, raw_scale, raw_rot, means3D=None, shell_logits=None, shell_cell_verts=None,
-                  shell_cells=None, keep_mask=None, means2D=None, use_softmax_for_bary_coords: bool = True, modes=None):
+                  shell_cells=None, keep_mask=None, means2D=None, use_softmax_for_bary_coords: bool = True, modes=None,
+                  sh_rotations=None):
     """-> (image [3,H,W], radii [P]).  settings: GaussianRasterizationSettings.  Exactly one of ``means3D`` [P,3]
     and (``shell_logits`` [P,6], ``shell_cell_verts`` [F,2,3,3] or [F,6,3], ``shell_cells`` [P] int64).
     raw_opacity [P] or [P,1]; raw_scale [P,3]; raw_rot [P,4]; shs [P,K,3].
     means2D (optional, [P,3] zeros with requires_grad, as the reference's callers pass it): receives the screen-space
     gradient (``viewspace_points.grad``) that densification reads.
     use_softmax_for_bary_coords = False: barycentric weights = relu(x) / sum relu(x) (frosting_model.py:716-718).
-    modes: per-call forward modes {'exact_blend', 'tight_binning', 'async_sh'} overriding frg_set_option for this call."""
+    modes: per-call forward modes {'exact_blend', 'tight_binning', 'async_sh'} overriding frg_set_option for this call.
+    sh_rotations (optional, float32 [P,3,3]): the SH colour of Gaussian i is evaluated at d @ R_i (GaussianRasterizer.forward);
+    no gradient for the matrices."""
     if (means3D is None) == (shell_logits is None):
         raise Exception("Please provide exactly one of either means3D or the shell parameterisation!")
     opts = {"modes": modes, "use_softmax_for_bary_coords": use_softmax_for_bary_coords}
     return _RasterizeRaw.apply(settings, opts, shs, raw_opacity, raw_scale, raw_rot, means3D, shell_logits, shell_cell_verts,
-                               shell_cells, keep_mask, means2D)
+                               shell_cells, keep_mask, means2D, sh_rotations)

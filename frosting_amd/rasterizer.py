@@ -32,6 +32,13 @@ def _f32c(t, device):
     return t.contiguous()
 
 
+def check_sh_rotations(sh_rotations, P, device):
+    """[P,3,3] float32 on the Gaussians' device -> the contiguous tensor the C ABI reads (frg_forward_args::sh_rotations)."""
+    if tuple(sh_rotations.shape) != (P, 3, 3) or sh_rotations.dtype != torch.float32 or sh_rotations.device != device:
+        raise RuntimeError("sh_rotations must be a float32 tensor of shape (num_points, 3, 3) on the Gaussians' device")
+    return sh_rotations.detach().contiguous()
+
+
 class _NativeOps:
     """Drop-in for the reference's pybind module ``_C`` (DGR/ext.cpp:15-18):
     identical positional signatures and return tuples (DGR/rasterize_points.h:18-67)."""
@@ -39,13 +46,15 @@ class _NativeOps:
     @staticmethod
     def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                             viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree,
-                            campos, prefiltered, debug, keep_mask=None, modes=None):
+                            campos, prefiltered, debug, keep_mask=None, modes=None, sh_rotations=None):
         """keep_mask (extension, optional bool/uint8 [P]): Gaussians with a zero entry are left out of this
         view as if culled -- Frosting's occlusion culling without the boolean compaction of every
         per-Gaussian tensor (frosting_scene/frosting_model.py:1564-1586).
         modes (extension, optional dict): per-call forward modes {'exact_blend', 'tight_binning', 'async_sh'} that
         override the process-wide frg_set_option values for THIS call (frg_forward_args); 'forward_only': 1 = no backward
-        will follow, the forward keeps nothing for one (frg_forward_args::forward_only)."""
+        will follow, the forward keeps nothing for one (frg_forward_args::forward_only).
+        sh_rotations (extension, optional float32 [P,3,3], with sh): the SH colour of Gaussian i is evaluated at d @ R_i
+        instead of its view direction d (frg_forward_args::sh_rotations; frosting_model.py:1478-1485)."""
         if means3D.dim() != 2 or means3D.shape[1] != 3:
             raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:57-59
         if not means3D.is_cuda:
@@ -61,6 +70,8 @@ class _NativeOps:
             if keep_mask is not None and (keep_mask.shape != (P,) or keep_mask.device != dev or
                                           keep_mask.dtype not in (torch.bool, torch.uint8)):
                 raise RuntimeError("keep_mask must be a bool / uint8 tensor of shape (num_points,) on the Gaussians' device")
+            if sh_rotations is not None:
+                sh_rotations = check_sh_rotations(sh_rotations, P, dev)
             a = _lib.forward_args(
                 geometry_alloc=geom.cb, binning_alloc=binning.cb, image_alloc=img.cb, P=P, D=int(degree), M=M,
                 background=_f32c(background, dev), width=W, height=H, means3D=_f32c(means3D, dev), shs=_f32c(sh, dev),
@@ -69,8 +80,8 @@ class _NativeOps:
                 viewmatrix=_f32c(viewmatrix, dev), projmatrix=_f32c(projmatrix, dev), cam_pos=_f32c(campos, dev),
                 tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), prefiltered=int(bool(prefiltered)), out_color=out_color,
                 radii=radii, debug=int(bool(debug)), hip_stream=torch.cuda.current_stream(dev).cuda_stream,
-                keep_mask=None if keep_mask is None else keep_mask.contiguous(), modes=modes)
-            if keep_mask is None and modes is None:      # the reference-shaped entry point (rasterizer.h:33-56)
+                keep_mask=None if keep_mask is None else keep_mask.contiguous(), modes=modes, sh_rotations=sh_rotations)
+            if keep_mask is None and modes is None and sh_rotations is None:      # the reference-shaped entry point (rasterizer.h:33-56)
                 rc = L.frg_forward(*_lib.positional(a, _lib.FORWARD_POSITIONAL))
             else:
                 rc = L.frg_forward_ex(C.byref(a))
@@ -101,6 +112,24 @@ class _NativeOps:
         return _NativeOps.rasterize_gaussians(*args[:19], keep_mask=mask, modes=modes)
 
     @staticmethod
+    def rasterize_gaussians_rot(*args):
+        """(the 22 arguments of rasterize_gaussians_ex, sh_rotations [P,3,3] or an empty tensor) -- same name as the compiled
+        module's export."""
+        mask = args[19] if args[19] is not None and args[19].numel() else None
+        modes = {"forward_only": int(bool(args[21]))}
+        if int(args[20]) >= 0:
+            modes["exact_blend"] = int(args[20])
+        rot = args[22] if args[22] is not None and args[22].numel() else None
+        return _NativeOps.rasterize_gaussians(*args[:19], keep_mask=mask, modes=modes, sh_rotations=rot)
+
+    @staticmethod
+    def rasterize_gaussians_backward_rot(*args):
+        """(the 22 arguments of rasterize_gaussians_backward_ex, the forward's sh_rotations or an empty tensor) -- same name as
+        the compiled module's export."""
+        rot = args[22] if args[22] is not None and args[22].numel() else None
+        return _NativeOps.rasterize_gaussians_backward(*args[:21], exact_blend=int(args[21]), sh_rotations=rot)
+
+    @staticmethod
     def get_option(name):
         return _lib.get_option(name)
 
@@ -113,9 +142,11 @@ class _NativeOps:
     @staticmethod
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                      cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
-                                     degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, exact_blend=-1):
+                                     degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, exact_blend=-1,
+                                     sh_rotations=None):
         """exact_blend (extension): -1 = the arithmetic of the forward that filled the buffers (what the library remembers
-        of it, else what that forward stamped into imageBuffer); 0 | 1 = stated by the caller (frg_backward_args::exact_blend)."""
+        of it, else what that forward stamped into imageBuffer); 0 | 1 = stated by the caller (frg_backward_args::exact_blend).
+        sh_rotations (extension): the forward's matrices, None exactly when it had none (frg_backward_args::sh_rotations)."""
         L = _lib.lib()
         dev = means3D.device
         P = int(means3D.shape[0])
@@ -128,6 +159,8 @@ class _NativeOps:
             has_sr = scales is not None and scales.numel() != 0
             dL_dmeans3D, dL_dmeans2D, dL_dcolors = e(P, 3), e(P, 3), e(P, 3)
             dL_dopacity, dL_dcov3D = e(P, 1), e(P, 6)   # dL_dconic is an intermediate the reference never returns (:195)
+            if sh_rotations is not None:
+                sh_rotations = check_sh_rotations(sh_rotations, P, dev)
             # rows the kernels do not write (absent input) stay zero, as in the reference's zero-allocated outputs
             dL_dsh = e(P, M, 3) if has_sh else torch.zeros((P, M, 3), dtype=torch.float32, device=dev)
             dL_dscales = e(P, 3) if has_sr else torch.zeros((P, 3), dtype=torch.float32, device=dev)
@@ -145,8 +178,9 @@ class _NativeOps:
                     dL_dmean2D=dL_dmeans2D, dL_dopacity=dL_dopacity, dL_dcolor=dL_dcolors, dL_dmean3D=dL_dmeans3D,
                     dL_dcov3D=dL_dcov3D, dL_dsh=dL_dsh if has_sh else None, dL_dscale=dL_dscales if has_sr else None,
                     dL_drot=dL_drotations if has_sr else None, workspace=workspace, workspace_bytes=ws_bytes,
-                    debug=int(bool(debug)), hip_stream=torch.cuda.current_stream(dev).cuda_stream, exact_blend=int(exact_blend) + 1)
-                if int(exact_blend) < 0:      # the reference-shaped entry point (rasterizer.h:58-84)
+                    debug=int(bool(debug)), hip_stream=torch.cuda.current_stream(dev).cuda_stream, exact_blend=int(exact_blend) + 1,
+                    sh_rotations=sh_rotations)
+                if int(exact_blend) < 0 and sh_rotations is None:      # the reference-shaped entry point (rasterizer.h:58-84)
                     rc = L.frg_backward(*_lib.positional(a, _lib.BACKWARD_POSITIONAL))
                 else:
                     rc = L.frg_backward_ex(C.byref(a))
@@ -203,7 +237,7 @@ def _make_autograd_function(ops):
 
         @staticmethod
         def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                    raster_settings, keep_mask=None):
+                    raster_settings, keep_mask=None, sh_rotations=None):
             s = raster_settings
             native_args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
                            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh,
@@ -217,8 +251,15 @@ def _make_autograd_function(ops):
             # depends neither on what the library remembers of this forward nor on the option's value by then.
             carried = hasattr(ops, "rasterize_gaussians_ex") and hasattr(ops, "rasterize_gaussians_backward_ex")
             exact = int(ops.get_option("exact_blend")) if carried else -1
+            if sh_rotations is not None:
+                if not (hasattr(ops, "rasterize_gaussians_rot") and hasattr(ops, "rasterize_gaussians_backward_rot")):
+                    raise RuntimeError("this native binding has no rasterize_gaussians_rot export: sh_rotations cannot be rendered")
+                sh_rotations = check_sh_rotations(sh_rotations, int(means3D.shape[0]), means3D.device)
 
             def run():
+                if sh_rotations is not None:
+                    return ops.rasterize_gaussians_rot(*native_args, keep_mask if keep_mask is not None else torch.empty(0),
+                                                       exact, forward_only, sh_rotations)
                 if carried:
                     return ops.rasterize_gaussians_ex(*native_args, keep_mask if keep_mask is not None else torch.empty(0),
                                                       exact, forward_only)
@@ -241,14 +282,16 @@ def _make_autograd_function(ops):
             ctx.raster_settings = s
             ctx.num_rendered = num_rendered
             ctx.exact_blend, ctx.forward_only = exact, forward_only
-            ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img)
+            ctx.rotated = sh_rotations is not None
+            ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img,
+                                  *([sh_rotations] if ctx.rotated else []))
             ctx.mark_non_differentiable(radii)
             return color, radii
 
         @staticmethod
         def backward(ctx, grad_out_color, _grad_radii):
             s = ctx.raster_settings
-            colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
+            colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors[:10]
             native_args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
                            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color, sh, s.sh_degree, s.campos,
                            geom, ctx.num_rendered, binning, img, s.debug)
@@ -256,7 +299,10 @@ def _make_autograd_function(ops):
                 raise RuntimeError("backward of a forward that was run with no input requiring a gradient (forward_only): "
                                    "nothing was kept for it")
             backward_op = ops.rasterize_gaussians_backward
-            if ctx.exact_blend >= 0:          # the forward's arithmetic, carried by this ctx
+            if ctx.rotated:                   # ... and the forward's matrices
+                def backward_op(*a):
+                    return ops.rasterize_gaussians_backward_rot(*a, ctx.exact_blend, ctx.saved_tensors[10])
+            elif ctx.exact_blend >= 0:        # the forward's arithmetic, carried by this ctx
                 def backward_op(*a):
                     return ops.rasterize_gaussians_backward_ex(*a, ctx.exact_blend)
             if s.debug:
@@ -270,7 +316,7 @@ def _make_autograd_function(ops):
             else:
                 grads = backward_op(*native_args)
             g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rots = grads
-            return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov3D, None, None
+            return g_means3D, g_means2D, g_sh, g_colors, g_opac, g_scales, g_rots, g_cov3D, None, None, None
 
     return _RasterizeGaussians
 
@@ -279,9 +325,9 @@ _RasterizeGaussians = _make_autograd_function(_C)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, keep_mask=None):
+                        raster_settings, keep_mask=None, sh_rotations=None):
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, keep_mask)
+                                     cov3Ds_precomp, raster_settings, keep_mask, sh_rotations)
 
 
 class GaussianRasterizer(nn.Module):
@@ -301,11 +347,16 @@ class GaussianRasterizer(nn.Module):
             return self._ops.mark_visible(positions, s.viewmatrix, s.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, keep_mask=None):
+                cov3D_precomp=None, keep_mask=None, sh_rotations=None):
         """keep_mask: extension over the reference signature (optional bool [P]); see
-        _NativeOps.rasterize_gaussians."""
+        _NativeOps.rasterize_gaussians.
+        sh_rotations: extension (optional float32 [P,3,3], with shs): the SH colour of Gaussian i is evaluated at d @ R_i --
+        the edited / animated scenes of the reference, which evaluates these colours in eager torch and passes
+        colors_precomp (frosting_model.py:1478-1485).  No gradient for the matrices."""
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+        if sh_rotations is not None and colors_precomp is not None:
+            raise Exception('Please provide sh_rotations only together with SHs, not with precomputed colors!')
         have_sr = scales is not None and rotations is not None
         partial_sr = (scales is not None) or (rotations is not None)
         if (not have_sr and cov3D_precomp is None) or (partial_sr and cov3D_precomp is not None):
@@ -319,7 +370,7 @@ class GaussianRasterizer(nn.Module):
             empty if scales is None else scales,
             empty if rotations is None else rotations,
             empty if cov3D_precomp is None else cov3D_precomp,
-            self.raster_settings, keep_mask)
+            self.raster_settings, keep_mask, sh_rotations)
 
 
 def make_rasterizer_class(ops):

@@ -63,11 +63,15 @@ def sh_to_rgb(sh):
 RGB2SH, SH2RGB = rgb_to_sh, sh_to_rgb
 
 
-def points_rgb(means3D, shs, campos, deg):
+def points_rgb(means3D, shs, campos, deg, sh_rotations=None):
     """View-dependent colour exactly as the rasterizer derives it
     (Frosting.get_points_rgb, frosting_model.py:1304-1352): normalised
-    direction from the camera, SH evaluation, +0.5, clamp at 0.  shs is [P,K,3]."""
+    direction from the camera, SH evaluation, +0.5, clamp at 0.  shs is [P,K,3].
+    sh_rotations ([P,3,3], optional): the direction of Gaussian i becomes d @ R_i, the matrix used as given
+    (the sh_rotations branch of render_image_gaussian_rasterizer, frosting_model.py:1478-1485)."""
     d = means3D - campos.reshape(1, 3)
     d = d / d.norm(dim=-1, keepdim=True)
+    if sh_rotations is not None:
+        d = (d.unsqueeze(1) @ sh_rotations)[..., 0, :]
     col = eval_sh(deg, shs.transpose(-1, -2), d) + 0.5
     return col.clamp_min(0.0)

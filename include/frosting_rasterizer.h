@@ -162,6 +162,20 @@ typedef struct frg_forward_args {
      * does not remember the forward reads that stamp.  Not offered with instance_capacity > 0.  The binning chunk is sized
      * as without it: the checkpoints' 8 ... 16 bytes per instance are carved and left unwritten. */
     int forward_only;
+    /* ---- fifth generation ---------------------------------------------------------------------------------------
+     * sh_rotations (optional, [P,3,3] float32, row-major, contiguous; together with shs, never with colors_precomp): the
+     * SH colour of Gaussian i is evaluated at d' = d @ R_i instead of its unit view direction d --
+     * d'[j] = d[0] R[0][j] + d[1] R[1][j] + d[2] R[2][j], float32, left to right, no contraction.  This is how the reference
+     * renders edited and animated scenes (frosting_model.py:1478-1485 forms these directions, evaluates the SH in eager torch
+     * over all P Gaussians and passes colors_precomp; here only the Gaussians that survive culling and keep_mask read their
+     * 36 bytes).  The matrix is used AS GIVEN: neither orthonormalised nor is d' renormalised.  +0.5, the clamp and its
+     * bits, radii, tile lists and the blend do not change; NULL is the behaviour of the earlier generations bit for bit.
+     * Offered on the blocking and the deferred forward, with every other field of this struct.  The forward stamps "directions
+     * were rotated" into the image chunk beside the blend mode: frg_backward_ex must be given the same matrices
+     * (frg_backward_args::sh_rotations) and refuses a mismatch either way with FRG_EINVAL, also on copies of the buffers.
+     * The view-parallel exchanges (frg_sh_color_grad, frg_pack_sum_rows, a backward with dL_dsh == NULL) refuse such a
+     * forward: rotations are a single-view render feature. */
+    const float* sh_rotations;
 } frg_forward_args;
 int frg_forward_ex(const frg_forward_args* args);
 
@@ -258,6 +272,11 @@ typedef struct frg_backward_args {
      * [0, P); each call's share of the sums (and of what frg_pack_sum_rows packs from them) is complete when that call's work
      * is, so a slot-sum exchange can pack and send range k while range k + 1 is still being reduced.  Same bits as one call. */
     int range_first, range_count;
+    /* sixth generation: sh_rotations, the [P,3,3] matrices of the forward that filled the buffers (frg_forward_args::sh_rotations;
+     * NULL exactly when that forward had none -- anything else is refused with FRG_EINVAL).  dL_dsh uses the basis at
+     * d' = d @ R; the direction term of dL_dmean3D is R . dL/dd' pushed through the normalisation of the UNROTATED offset.
+     * The matrices themselves get no gradient. */
+    const float* sh_rotations;
 } frg_backward_args;
 int frg_backward_ex(const frg_backward_args* args);
 
