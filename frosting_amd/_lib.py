@@ -124,6 +124,37 @@ class CombineArgs(C.Structure):
                 ("hip_stream", C.c_void_p)]
 
 
+class PackSumArgs(C.Structure):
+    """frg_pack_sum_args (include/frosting_rasterizer.h)."""
+    _fields_ = [("struct_size", C.c_size_t),
+                ("P", C.c_int), ("R", C.c_int), ("first", C.c_int), ("count", C.c_int),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("drgb_masked", C.c_void_p), ("viewmatrix", C.c_void_p), ("projmatrix", C.c_void_p), ("campos", C.c_void_p),
+                ("tan_fovx", C.c_float), ("tan_fovy", C.c_float),
+                ("width", C.c_int), ("height", C.c_int),
+                ("scale_modifier", C.c_float),
+                ("D", C.c_int),
+                ("packet", C.c_void_p), ("packet_bytes", C.c_size_t),
+                ("capacity_rows", C.c_longlong),
+                ("radii", C.c_void_p),
+                ("hip_stream", C.c_void_p)]
+
+
+class DensifyViewsArgs(C.Structure):
+    """frg_densify_views_args (include/frosting_rasterizer.h)."""
+    _fields_ = [("struct_size", C.c_size_t),
+                ("P", C.c_int), ("first", C.c_int), ("count", C.c_int), ("n_views", C.c_int),
+                ("packets", C.c_void_p),
+                ("packet_stride_bytes", C.c_size_t),
+                ("capacity_rows", C.c_longlong),
+                ("means3D", C.c_void_p), ("scales", C.c_void_p), ("rotations", C.c_void_p), ("opacities", C.c_void_p),
+                ("raw_opacities", C.c_void_p), ("raw_scales", C.c_void_p), ("raw_rotations", C.c_void_p),
+                ("xyz_gradient_accum", C.c_void_p), ("denom", C.c_void_p), ("max_radii2D", C.c_void_p),
+                ("status", C.c_void_p),
+                ("status_seq", C.c_uint),
+                ("hip_stream", C.c_void_p)]
+
+
 class DensifyParams(C.Structure):
     """frg_densify_params (include/frosting_rasterizer.h)."""
     _fields_ = [("struct_size", C.c_size_t),
@@ -343,6 +374,13 @@ def lib():
                                         C.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp]
         L.frg_reset_opacity.restype = i
         L.frg_reset_opacity.argtypes = [i, vp, vp, vp, vp]
+    if hasattr(L, "frg_densify_accumulate_views"):
+        L.frg_sum_packet_bytes_ex.restype = sz
+        L.frg_sum_packet_bytes_ex.argtypes = [i, C.c_longlong, i]
+        L.frg_pack_sum_rows_ex.restype = i
+        L.frg_pack_sum_rows_ex.argtypes = [C.POINTER(PackSumArgs)]
+        L.frg_densify_accumulate_views.restype = i
+        L.frg_densify_accumulate_views.argtypes = [C.POINTER(DensifyViewsArgs)]
     _lib = L
     return L
 
@@ -396,4 +434,5 @@ EXPORTED_SYMBOLS = [
     "frg_photometric_workspace_bytes", "frg_photometric_loss", "frg_activate", "frg_activate_backward",
     "frg_knn_workspace_bytes", "frg_knn_mean_dist2", "frg_shell_points", "frg_shell_points_backward",
     "frg_densify_accumulate", "frg_densify_workspace_bytes", "frg_densify_plan", "frg_densify_apply", "frg_reset_opacity",
+    "frg_sum_packet_bytes_ex", "frg_pack_sum_rows_ex", "frg_densify_accumulate_views",
 ]

@@ -67,25 +67,48 @@ size_t frg_sum_packet_bytes(int n_gaussians, long long capacity_rows)
     return frg::sum_packet_bytes((size_t)n_gaussians, (size_t)capacity_rows);
 }
 
+size_t frg_sum_packet_bytes_ex(int n_gaussians, long long capacity_rows, int with_visibility)
+{
+    if (n_gaussians < 0 || capacity_rows < 0) return 0;
+    return with_visibility ? frg::sum_packet_bytes_visible((size_t)n_gaussians, (size_t)capacity_rows)
+                           : frg::sum_packet_bytes((size_t)n_gaussians, (size_t)capacity_rows);
+}
+
+int frg_pack_sum_rows_ex(const frg_pack_sum_args* a)
+{
+    if (!a || a->struct_size != sizeof(frg_pack_sum_args))
+        return fail(FRG_EINVAL, "frg_pack_sum_args: struct_size %zu, this library expects %zu", a ? a->struct_size : (size_t)0, sizeof(frg_pack_sum_args));
+    if (a->P < 0 || a->R < 0 || a->first < 0 || a->count < 0 || (long long)a->first + a->count > a->P || a->first % 64 != 0)
+        return fail(FRG_EINVAL, "bad range: P=%d first=%d (a multiple of 64) count=%d", a->P, a->first, a->count);
+    if (a->capacity_rows < 0 || a->capacity_rows > 0x7fffffffLL) return fail(FRG_EINVAL, "capacity_rows %lld", a->capacity_rows);
+    if (!a->workspace || a->workspace_bytes < frg_backward_workspace_bytes(a->P, a->R)) return fail(FRG_EALLOC, "not the workspace of a backward with P=%d R=%d", a->P, a->R);
+    if (frg::phase1_was_rotated(a->workspace)) return fail(FRG_EINVAL, "frg_pack_sum_rows: %s", frg::kRotatedSingleView);
+    const size_t need = frg_sum_packet_bytes_ex(a->count, a->capacity_rows, a->radii != nullptr);
+    if (!a->packet || a->packet_bytes < need || reinterpret_cast<uintptr_t>(a->packet) % 16 != 0)
+        return fail(FRG_EALLOC, "packet: need %zu bytes, 16-byte aligned", need);
+    if (!a->drgb_masked || !a->viewmatrix || !a->projmatrix || !a->campos) return fail(FRG_EINVAL, "null pointer");
+    if (a->width <= 0 || a->height <= 0 || a->D < 0 || a->D > 3) return fail(FRG_EINVAL, "bad view: %dx%d degree %d", a->width, a->height, a->D);
+    const frg::BwdWorkspace ws = frg::BwdWorkspace::carve(a->workspace, a->P, a->R);      // what phase 1 of that backward left
+    const frg::SumCamera cam{a->tan_fovx, a->tan_fovy, a->scale_modifier, a->width, a->height, a->D};
+    FRG_HIP(frg::launch_pack_sum_rows(a->first, a->count, (uint32_t)a->capacity_rows, ws.live_masks, ws.sums, ws.dir_terms, a->drgb_masked, cam, a->viewmatrix,
+                                      a->projmatrix, a->campos, a->packet, ws.group_tot, (hipStream_t)a->hip_stream, a->radii));
+    return FRG_OK;
+}
+
 int frg_pack_sum_rows(int P, int R, int first, int count, char* workspace, size_t workspace_bytes, const float* drgb_masked,
                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
                       int width, int height, float scale_modifier, int D, void* packet, size_t packet_bytes, long long capacity_rows,
                       void* hip_stream)
 {
-    if (P < 0 || R < 0 || first < 0 || count < 0 || (long long)first + count > P || first % 64 != 0)
-        return fail(FRG_EINVAL, "bad range: P=%d first=%d (a multiple of 64) count=%d", P, first, count);
-    if (capacity_rows < 0 || capacity_rows > 0x7fffffffLL) return fail(FRG_EINVAL, "capacity_rows %lld", capacity_rows);
-    if (!workspace || workspace_bytes < frg_backward_workspace_bytes(P, R)) return fail(FRG_EALLOC, "not the workspace of a backward with P=%d R=%d", P, R);
-    if (frg::phase1_was_rotated(workspace)) return fail(FRG_EINVAL, "frg_pack_sum_rows: %s", frg::kRotatedSingleView);
-    if (!packet || packet_bytes < frg_sum_packet_bytes(count, capacity_rows) || reinterpret_cast<uintptr_t>(packet) % 16 != 0)
-        return fail(FRG_EALLOC, "packet: need %zu bytes, 16-byte aligned", frg_sum_packet_bytes(count, capacity_rows));
-    if (!drgb_masked || !viewmatrix || !projmatrix || !campos) return fail(FRG_EINVAL, "null pointer");
-    if (width <= 0 || height <= 0 || D < 0 || D > 3) return fail(FRG_EINVAL, "bad view: %dx%d degree %d", width, height, D);
-    const frg::BwdWorkspace ws = frg::BwdWorkspace::carve(workspace, P, R);      // what phase 1 of that backward left
-    const frg::SumCamera cam{tan_fovx, tan_fovy, scale_modifier, width, height, D};
-    FRG_HIP(frg::launch_pack_sum_rows(first, count, (uint32_t)capacity_rows, ws.live_masks, ws.sums, ws.dir_terms, drgb_masked, cam, viewmatrix, projmatrix,
-                                      campos, packet, ws.group_tot, (hipStream_t)hip_stream));
-    return FRG_OK;
+    frg_pack_sum_args a{};
+    a.struct_size = sizeof(a);
+    a.P = P; a.R = R; a.first = first; a.count = count;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    a.drgb_masked = drgb_masked; a.viewmatrix = viewmatrix; a.projmatrix = projmatrix; a.campos = campos;
+    a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy; a.width = width; a.height = height; a.scale_modifier = scale_modifier; a.D = D;
+    a.packet = packet; a.packet_bytes = packet_bytes; a.capacity_rows = capacity_rows;
+    a.radii = nullptr; a.hip_stream = hip_stream;
+    return frg_pack_sum_rows_ex(&a);
 }
 
 size_t frg_combine_workspace_bytes(int n_views, long long capacity_rows)
@@ -344,6 +367,34 @@ int frg_densify_accumulate(int P, const int* radii, const float* dL_dmean2D, con
     if (!radii || !dL_dmean2D || !xyz_gradient_accum || !denom || !max_radii2D) return fail(FRG_EINVAL, "null pointer");
     FRG_HIP(frg::launch_densify_accumulate(P, radii, dL_dmean2D, row_live, xyz_gradient_accum, denom, max_radii2D,
                                            (hipStream_t)hip_stream));
+    return FRG_OK;
+}
+
+int frg_densify_accumulate_views(const frg_densify_views_args* a)
+{
+    if (!a || a->struct_size != sizeof(frg_densify_views_args))
+        return fail(FRG_EINVAL, "frg_densify_views_args: struct_size %zu, this library expects %zu", a ? a->struct_size : (size_t)0,
+                    sizeof(frg_densify_views_args));
+    if (a->P < 0 || a->first < 0 || a->count < 0 || (long long)a->first + a->count > a->P || a->first % 64 != 0)
+        return fail(FRG_EINVAL, "bad range: P=%d first=%d (a multiple of 64) count=%d", a->P, a->first, a->count);
+    if (a->n_views < 1 || a->n_views > 16) return fail(FRG_EINVAL, "1..16 views expected, got %d", a->n_views);
+    if (a->capacity_rows < 0 || a->capacity_rows >= 65535LL * 256) return fail(FRG_EINVAL, "capacity_rows %lld: a packet holds fewer than 2^24 rows", a->capacity_rows);
+    if (a->count == 0) return FRG_OK;
+    const size_t need = frg_sum_packet_bytes_ex(a->count, a->capacity_rows, 1);
+    if (!a->packets || a->packet_stride_bytes % 16 != 0 || a->packet_stride_bytes < need || reinterpret_cast<uintptr_t>(a->packets) % 16 != 0)
+        return fail(FRG_EINVAL, "packets: stride %zu, a packet of %d Gaussians and %lld rows with its visibility section has %zu bytes (16-byte aligned)",
+                    a->packet_stride_bytes, a->count, a->capacity_rows, need);
+    if (!a->means3D) return fail(FRG_EINVAL, "means3D is required (shell-bound centres are not offered here)");
+    if ((a->opacities == nullptr) == (a->raw_opacities == nullptr)) return fail(FRG_EINVAL, "provide exactly one of opacities / raw_opacities");
+    const bool raw_sr = a->raw_scales && a->raw_rotations;
+    if (raw_sr == (a->scales && a->rotations) || (a->raw_scales == nullptr) != (a->raw_rotations == nullptr) || (a->scales == nullptr) != (a->rotations == nullptr))
+        return fail(FRG_EINVAL, "provide (scales, rotations) or (raw_scales, raw_rotations)");
+    if (reinterpret_cast<uintptr_t>(a->rotations) % 16 != 0) return fail(FRG_EINVAL, "rotations must be 16-byte aligned");
+    if (!a->xyz_gradient_accum || !a->denom || !a->max_radii2D) return fail(FRG_EINVAL, "null statistics pointer");
+    frg::FwdInputs in{a->means3D, a->scales, a->rotations, a->opacities, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    in.raw.raw_opacity = a->raw_opacities; in.raw.raw_scale = a->raw_scales; in.raw.raw_rot = a->raw_rotations;
+    FRG_HIP(frg::launch_densify_views(a->first, a->count, a->n_views, a->packets, a->packet_stride_bytes, (uint32_t)a->capacity_rows, in,
+                                      a->xyz_gradient_accum, a->denom, a->max_radii2D, a->status, a->status_seq, (hipStream_t)a->hip_stream));
     return FRG_OK;
 }
 

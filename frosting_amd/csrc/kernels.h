@@ -147,16 +147,23 @@ hipError_t launch_scatter_grad_rows(unsigned int n, int P, const float* rows, fl
 #define FRG_SUM_MAGIC 0x46534d36u
 struct SumCamera { float tan_fovx, tan_fovy, scale_modifier; int width, height, D; };
 size_t sum_packet_bytes(size_t n, size_t capacity);
+size_t sum_packet_bytes_visible(size_t n, size_t capacity);     // with the visibility section (one bit per Gaussian) behind the rows
 // live_masks: one bit per Gaussian, as phase 1 of the backward leaves them in its workspace; sums: [P][9] of the same workspace
 hipError_t launch_pack_sum_rows(int first, int n, uint32_t capacity, const unsigned long long* live_masks, const float* sums,
                                 const float* view_dir_terms, const float* drgb_masked, const SumCamera& cam, const float* viewmatrix, const float* projmatrix,
-                                const float* campos, void* packet, uint32_t* group_tot /* scratch: one word per 16384 Gaussians */, hipStream_t s);
+                                const float* campos, void* packet, uint32_t* group_tot /* scratch: one word per 16384 Gaussians */, hipStream_t s,
+                                const int* radii = nullptr /* given: the packet gets its visibility section (radii > 0) */);
 // in: means3D, shs, scales, rotations, opacities (or their raw forms); out: dL_dmean3D, dL_dscale, dL_drot, dL_dopacity, dL_dsh
 // workspace: combine_workspace_bytes(n_views, capacity) (256 bytes since the pass became one kernel that stages nothing in HBM);
 size_t combine_workspace_bytes(int n_views, size_t capacity);
 hipError_t launch_backward_combine(int first, int n, int n_views, const void* packets, size_t packet_stride_bytes, uint32_t capacity,
                                    const FwdInputs& in, const BwdOutputs& out, unsigned long long* status, uint32_t seq, unsigned char* row_live,
                                    char* workspace, hipStream_t s);
+// densification statistics of n_views views from their packets (with visibility sections), in view order: what
+// launch_densify_accumulate adds view by view.  in: means3D, scales, rotations, opacities (or their raw forms)
+hipError_t launch_densify_views(int first, int n, int n_views, const void* packets, size_t packet_stride_bytes, uint32_t capacity,
+                                const FwdInputs& in, float* accum, float* denom, float* max_radii2D, unsigned long long* status, uint32_t seq,
+                                hipStream_t s);
 
 // fused Adam over the flat parameter layout (adam.hip)
 #ifndef FRG_ADAM_MAX_SEGMENTS

@@ -35,10 +35,14 @@ namespace frg {
 //   masks   uint64[nblk]  at word 64                 (nblk = blocks of 64 Gaussians)
 //   bases   uint32[nblk]  behind them, 16-byte aligned
 //   rows    float[capacity][12] behind them, 16-byte aligned
+//   visible uint64[nblk]  behind the rows, 16-byte aligned -- OPTIONAL (frg_pack_sum_rows_ex with radii): bit g % 64 of word g / 64 =
+//           radii[first + g] > 0; header word [6] = the section's word offset, 0 = the packet has none
 __host__ __device__ inline size_t sum_packet_blocks(size_t n) { return (n + 63) / 64; }
 __host__ __device__ inline size_t sum_packet_bases_word(size_t n) { return FRG_SUM_HDR_WORDS + 2 * sum_packet_blocks(n); }
 __host__ __device__ inline size_t sum_packet_rows_word(size_t n) { return (sum_packet_bases_word(n) + sum_packet_blocks(n) + 3) / 4 * 4; }
 size_t sum_packet_bytes(size_t n, size_t capacity) { return ((sum_packet_rows_word(n) + FRG_SUM_ROW_FLOATS * capacity + 3) / 4 * 4) * 4; }
+__host__ __device__ inline size_t sum_packet_visible_word(size_t n, size_t capacity) { return (sum_packet_rows_word(n) + FRG_SUM_ROW_FLOATS * capacity + 3) / 4 * 4; }
+size_t sum_packet_bytes_visible(size_t n, size_t capacity) { return ((sum_packet_visible_word(n, capacity) + 2 * sum_packet_blocks(n) + 3) / 4 * 4) * 4; }
 
 // Pack, two launches over the packet's blocks of 64 Gaussians:
 //   sum_rows_local_kernel   one thread per block, 256 blocks per workgroup: the mask word (copied from the phase-1 workspace),
@@ -49,6 +53,8 @@ size_t sum_packet_bytes(size_t n, size_t capacity) { return ((sum_packet_rows_wo
 //                           the first wave writes the header (rows wanted = the sum of all totals, the camera).
 // (Round 6's first forms scanned all blocks in ONE workgroup: 70, 30 and again 70 us per packet of 47 000 blocks -- one CU's
 // load path.)
+// VIS (frg_pack_sum_rows_ex with radii): the wave that packs a block of 64 Gaussians also ballots radii > 0 over it -- the
+// packet's visibility section, what the densification statistics of the view need beside its rows (densify_views_kernel).
 #define SUM_GROUP 256
 __global__ void __launch_bounds__(SUM_GROUP)
 sum_rows_local_kernel(int first, int n, const unsigned long long* __restrict__ live_masks, uint32_t* __restrict__ packet,
@@ -71,14 +77,21 @@ sum_rows_local_kernel(int first, int n, const unsigned long long* __restrict__ l
     if (tid == 0) group_tot[blockIdx.x] = total;
 }
 
+template <bool VIS>
 __global__ void __launch_bounds__(256)
 sum_rows_pack_kernel(int first, int n, uint32_t capacity, const float* __restrict__ sums, const float* __restrict__ view_dir_terms,
                      const float* __restrict__ drgb_masked, uint32_t* __restrict__ packet, const uint32_t* __restrict__ group_tot, SumCamera cam,
-                     const float* __restrict__ viewmatrix, const float* __restrict__ projmatrix, const float* __restrict__ campos)
+                     const float* __restrict__ viewmatrix, const float* __restrict__ projmatrix, const float* __restrict__ campos,
+                     const int* __restrict__ radii)
 {
     const int lane = threadIdx.x & 63, blk = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int nblk = (int)sum_packet_blocks((size_t)n);
     if (blk >= nblk) return;
+    if (VIS) {
+        const int gl = blk * 64 + lane;
+        const unsigned long long seen = __builtin_amdgcn_ballot_w64(gl < n && radii[(size_t)first + gl] > 0);
+        if (lane == 0) reinterpret_cast<unsigned long long*>(packet + sum_packet_visible_word((size_t)n, (size_t)capacity))[blk] = seen;
+    }
     const int ngroups = (nblk + SUM_GROUP - 1) / SUM_GROUP, grp = blk / SUM_GROUP;
     // rows before this block's group (and, for the header, of all groups)
     uint32_t before = 0, all = 0;
@@ -96,7 +109,7 @@ sum_rows_pack_kernel(int first, int n, uint32_t capacity, const float* __restric
             packet[0] = all < capacity ? all : capacity;
             packet[1] = all;
             packet[2] = (uint32_t)n; packet[3] = capacity; packet[4] = (uint32_t)first; packet[5] = FRG_SUM_MAGIC;
-            packet[6] = 0u; packet[7] = 0u;
+            packet[6] = VIS ? (uint32_t)sum_packet_visible_word((size_t)n, (size_t)capacity) : 0u; packet[7] = 0u;
             f[43] = cam.tan_fovx; f[44] = cam.tan_fovy;
             packet[45] = (uint32_t)cam.width; packet[46] = (uint32_t)cam.height;
             f[47] = cam.scale_modifier; packet[48] = (uint32_t)cam.D;
@@ -120,13 +133,17 @@ sum_rows_pack_kernel(int first, int n, uint32_t capacity, const float* __restric
 
 hipError_t launch_pack_sum_rows(int first, int n, uint32_t capacity, const unsigned long long* live_masks, const float* sums,
                                 const float* view_dir_terms, const float* drgb_masked, const SumCamera& cam, const float* viewmatrix, const float* projmatrix,
-                                const float* campos, void* packet, uint32_t* group_tot, hipStream_t s)
+                                const float* campos, void* packet, uint32_t* group_tot, hipStream_t s, const int* radii)
 {
     uint32_t* pk = reinterpret_cast<uint32_t*>(packet);
     const int nblk = (int)sum_packet_blocks((size_t)n);
     hipLaunchKernelGGL(sum_rows_local_kernel, dim3((nblk + SUM_GROUP - 1) / SUM_GROUP), dim3(SUM_GROUP), 0, s, first, n, live_masks, pk, group_tot);
-    hipLaunchKernelGGL(sum_rows_pack_kernel, dim3((nblk + 3) / 4), dim3(256), 0, s, first, n, capacity, sums, view_dir_terms, drgb_masked, pk, group_tot, cam,
-                       viewmatrix, projmatrix, campos);
+    if (radii)
+        hipLaunchKernelGGL(sum_rows_pack_kernel<true>, dim3((nblk + 3) / 4), dim3(256), 0, s, first, n, capacity, sums, view_dir_terms, drgb_masked, pk, group_tot,
+                           cam, viewmatrix, projmatrix, campos, radii);
+    else
+        hipLaunchKernelGGL(sum_rows_pack_kernel<false>, dim3((nblk + 3) / 4), dim3(256), 0, s, first, n, capacity, sums, view_dir_terms, drgb_masked, pk, group_tot,
+                           cam, viewmatrix, projmatrix, campos, radii);
     return hipGetLastError();
 }
 
@@ -591,6 +608,96 @@ hipError_t launch_backward_combine(int first, int n, int n_views, const void* pa
     const bool raw = in.raw.raw_opacity || in.raw.raw_scale || in.raw.raw_rot;
     if (raw) launch_tile<true>(B, nblk, s, first, n, n_views, pk, stride_w, capacity, in, out, row_live, status, seq);
     else launch_tile<false>(B, nblk, s, first, n, n_views, pk, stride_w, capacity, in, out, row_live, status, seq);
+    return hipGetLastError();
+}
+
+// ---- densification statistics of every view, from the packets ---------------------------------------------------------------
+// What frg_densify_accumulate (densify.hip) adds for ONE view from that view's radii and dL_dmean2D, added here for EVERY view of
+// the step, in view order, from the gathered packets: a packet with a visibility section says which Gaussians the view saw
+// (denom += 1, max_radii2D = max(., radius)) and carries, for those with a row, the two pixel moments dL_dmean2D is formed from
+// (combine_one_view's expressions: accum += |dL_dmean2D.xy|); conic, opacity and the radius are recomputed from the replicated
+// parameters with the forward's own functions (preprocess.hip preprocess_one), bit-identically.  A visible Gaussian without a
+// row has a zero viewspace gradient: it adds sqrtf(0), as the one-view kernel does.
+// One wave per block of 64 Gaussians, one lane per Gaussian: a view's visibility word, mask word, row offset and camera are
+// wave-uniform (scalar loads); the three statistics are read once and written once, by the lanes some view saw.
+// EVERY wave first looks at all the views' headers (a few cache lines): one packet without the section, of another range or
+// capacity, or overflowed -- and the whole launch writes nothing but the status word.
+__global__ void __launch_bounds__(256)
+densify_views_kernel(int first, int n, int n_views, const uint32_t* __restrict__ packets, size_t packet_stride_words, uint32_t capacity,
+                     const float* __restrict__ means3D, const float* __restrict__ scales, const float* __restrict__ rotations,
+                     const float* __restrict__ opacities, RawInputs raw, float* __restrict__ accum, float* __restrict__ denom,
+                     float* __restrict__ max_radii2D, unsigned long long* __restrict__ status, uint32_t seq)
+{
+    const int lane = threadIdx.x & 63;
+    const int blk = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    const int nblk = (int)sum_packet_blocks((size_t)n);
+    const size_t bases_w = sum_packet_bases_word((size_t)n), rows_w = sum_packet_rows_word((size_t)n);
+    const size_t vis_w = sum_packet_visible_word((size_t)n, (size_t)capacity);
+    bool bad = false;
+    if (lane < n_views) {
+        const uint32_t* h = packets + (size_t)lane * packet_stride_words;
+        bad = h[1] > h[3] || h[5] != FRG_SUM_MAGIC || h[2] != (uint32_t)n || h[4] != (uint32_t)first || h[3] != capacity || h[6] != (uint32_t)vis_w;
+    }
+    const bool refused = __builtin_amdgcn_ballot_w64(bad) != 0ull;
+    if (status && blockIdx.x == 0 && threadIdx.x == 0)
+        __hip_atomic_store(status, ((unsigned long long)seq << 32) | (refused ? 1ull : 0ull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (refused || blk >= nblk) return;
+    unsigned long long seen_any = 0ull;
+    for (int v = 0; v < n_views; v++)
+        seen_any |= reinterpret_cast<const unsigned long long*>(packets + (size_t)v * packet_stride_words + vis_w)[blk];
+    const int gl = blk * 64 + lane;
+    if (!((seen_any >> lane) & 1ull) || gl >= n) return;
+    const int idx = first + gl;
+    const float3 mean = param_mean(means3D, raw, idx);
+    const float3 sc = param_scale(scales, raw, idx);
+    const float4 q = param_rot(rotations, raw, idx);
+    const float o = param_opacity(opacities, raw, idx);
+    float acc = accum[idx], den = denom[idx], rad = max_radii2D[idx];
+    for (int v = 0; v < n_views; v++) {
+        const uint32_t* pk = packets + (size_t)v * packet_stride_words;
+        const unsigned long long seen = reinterpret_cast<const unsigned long long*>(pk + vis_w)[blk];
+        if (!((seen >> lane) & 1ull)) continue;
+        const float* cam = reinterpret_cast<const float*>(pk) + 8;
+        // the forward's covariance, radius and conic (preprocess.hip preprocess_one; combine_one_view above)
+        float cov[6];
+        cov3d_from_scale_rot(sc, cam[CAM_SCALE], q, cov);
+        const Ewa e = ewa_setup(mean, cam[CAM_FX], cam[CAM_FY], cam[CAM_TANX], cam[CAM_TANY], cam + CAM_VIEW);
+        float a, b, c;
+        ewa_cov2d(e, cov, a, b, c);
+        a += 0.3f; c += 0.3f;
+        const float det = a * c - b * b;
+        const float mid = 0.5f * (a + c);
+        const float lambda1 = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
+        const float lambda2 = mid - sqrtf(fmaxf(0.1f, mid * mid - det));
+        const float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
+        rad = fmaxf(rad, (float)f2i(my_radius));
+        den = den + 1.0f;
+        float gx = 0.0f, gy = 0.0f;
+        const unsigned long long m = reinterpret_cast<const unsigned long long*>(pk + FRG_SUM_HDR_WORDS)[blk];
+        if ((m >> lane) & 1ull) {
+            const uint32_t row = (pk + bases_w)[blk] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (row < capacity) {
+                const float* r = reinterpret_cast<const float*>(pk) + rows_w + (size_t)row * FRG_SUM_ROW_FLOATS;
+                const float m3 = r[3], m4 = r[4];
+                const float half_w = 0.5f * (float)__float_as_int(cam[CAM_W]), half_h = 0.5f * (float)__float_as_int(cam[CAM_H]);
+                const float det_inv = 1.f / det;
+                const float4 kc = make_float4(c * det_inv, -b * det_inv, a * det_inv, o);
+                gx = -o * (kc.x * m3 + kc.y * m4) * half_w;
+                gy = -o * (kc.z * m4 + kc.y * m3) * half_h;
+            }
+        }
+        acc = acc + sqrtf(gx * gx + gy * gy);
+    }
+    accum[idx] = acc; denom[idx] = den; max_radii2D[idx] = rad;
+}
+
+hipError_t launch_densify_views(int first, int n, int n_views, const void* packets, size_t packet_stride_bytes, uint32_t capacity,
+                                const FwdInputs& in, float* accum, float* denom, float* max_radii2D, unsigned long long* status, uint32_t seq,
+                                hipStream_t s)
+{
+    const int nblk = (int)sum_packet_blocks((size_t)n);
+    hipLaunchKernelGGL(densify_views_kernel, dim3((nblk + 3) / 4), dim3(256), 0, s, first, n, n_views, reinterpret_cast<const uint32_t*>(packets),
+                       packet_stride_bytes / 4, capacity, in.means3D, in.scales, in.rotations, in.opacities, in.raw, accum, denom, max_radii2D, status, seq);
     return hipGetLastError();
 }
 

@@ -410,6 +410,47 @@ void DensifyAccumulateHIP(const torch::Tensor& radii, const torch::Tensor& dL_dm
              "frg_densify_accumulate");
 }
 
+// the statistics of every view of a view-parallel step from the gathered slot-sum packets (frg_densify_accumulate_views)
+void DensifyAccumulateViewsHIP(const torch::Tensor& packets, const int64_t first, const int64_t count, const int64_t capacity_rows,
+                               const torch::Tensor& means3D, const torch::Tensor& scales, const torch::Tensor& rotations,
+                               const torch::Tensor& opacities, const bool raw_params, torch::Tensor& xyz_gradient_accum,
+                               torch::Tensor& denom, torch::Tensor& max_radii2D, const torch::Tensor& status, const int64_t status_seq)
+{
+    TORCH_CHECK(packets.is_cuda(), "frosting_amd densify: tensors must live on a ROCm device (no CPU path)");
+    const torch::Device dev = packets.device();
+    const c10::hip::HIPGuard guard(dev.index());
+    TORCH_CHECK(packets.dim() == 2, "packets must be [n_views, words]");
+    check_on(packets, dev, torch::kInt32, -1, "packets");
+    const int64_t P = max_radii2D.numel();
+    check_on(means3D, dev, torch::kFloat32, 3 * P, "means3D");
+    check_on(scales, dev, torch::kFloat32, 3 * P, "scales");
+    check_on(rotations, dev, torch::kFloat32, 4 * P, "rotations");
+    check_on(opacities, dev, torch::kFloat32, P, "opacities");
+    check_on(xyz_gradient_accum, dev, torch::kFloat32, P, "xyz_gradient_accum");
+    check_on(denom, dev, torch::kFloat32, P, "denom");
+    check_on(max_radii2D, dev, torch::kFloat32, P, "max_radii2D");
+    const bool posts = status.defined() && status.numel() != 0;
+    if (posts)
+        TORCH_CHECK(status.scalar_type() == torch::kInt64 && status.is_contiguous() && (status.is_pinned() || status.device() == dev),
+                    "status: one int64 word in pinned host memory or on the device");
+    frg_densify_views_args a{};
+    a.struct_size = sizeof(a);
+    a.P = static_cast<int>(P); a.first = static_cast<int>(first); a.count = static_cast<int>(count);
+    a.n_views = static_cast<int>(packets.size(0));
+    a.packets = packets.data_ptr();
+    a.packet_stride_bytes = static_cast<size_t>(packets.size(1)) * 4;
+    a.capacity_rows = capacity_rows;
+    a.means3D = means3D.data_ptr<float>();
+    (raw_params ? a.raw_scales : a.scales) = scales.data_ptr<float>();
+    (raw_params ? a.raw_rotations : a.rotations) = rotations.data_ptr<float>();
+    (raw_params ? a.raw_opacities : a.opacities) = opacities.data_ptr<float>();
+    a.xyz_gradient_accum = xyz_gradient_accum.data_ptr<float>(); a.denom = denom.data_ptr<float>(); a.max_radii2D = max_radii2D.data_ptr<float>();
+    a.status = posts ? reinterpret_cast<unsigned long long*>(status.data_ptr()) : nullptr;
+    a.status_seq = static_cast<unsigned int>(status_seq);
+    a.hip_stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    check_rc(frg_densify_accumulate_views(&a), "frg_densify_accumulate_views");
+}
+
 // -> (plan [4,P] int32, record [8] int32 on the device)
 std::tuple<torch::Tensor, torch::Tensor>
 DensifyPlanHIP(const torch::Tensor& raw_scales, const torch::Tensor& raw_opacities, const torch::Tensor& xyz_gradient_accum,
@@ -503,6 +544,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("rasterize_gaussians_rot", &RasterizeGaussiansRotHIP);
     m.def("rasterize_gaussians_backward_rot", &RasterizeGaussiansBackwardRotHIP);
     m.def("densify_accumulate", &DensifyAccumulateHIP);
+    m.def("densify_accumulate_views", &DensifyAccumulateViewsHIP);
     m.def("densify_plan", &DensifyPlanHIP);
     m.def("densify_apply", &DensifyApplyHIP);
     m.def("reset_opacity", &ResetOpacityHIP);

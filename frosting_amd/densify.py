@@ -28,7 +28,7 @@ SECTIONS = ("kept", "cloned", "split_first", "split_second")
 
 
 class _CtypesOps:
-    """The four device operations over ctypes; diff_gaussian_rasterization._C exports the same four with the same
+    """The five device operations over ctypes; diff_gaussian_rasterization._C exports the same five with the same
     arguments (csrc/torch_ext/torch_binding.cpp)."""
 
     @staticmethod
@@ -39,6 +39,27 @@ class _CtypesOps:
                                                    _lib.ptr(xyz_gradient_accum), _lib.ptr(denom), _lib.ptr(max_radii2D),
                                                    _lib.stream_ptr(dev))
         _lib.check(rc, "frg_densify_accumulate")
+
+    @staticmethod
+    def densify_accumulate_views(packets, first, count, capacity_rows, means3D, scales, rotations, opacities, raw_params,
+                                 xyz_gradient_accum, denom, max_radii2D, status, status_seq):
+        """frg_densify_accumulate_views: packets [n_views, words] int32 as gathered (with visibility sections), Gaussians
+        [first, first + count); scales / rotations / opacities in their raw forms when raw_params; status: one int64 word
+        (pinned host or device memory) or an empty tensor."""
+        dev = packets.device
+        v = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        raw = bool(raw_params)
+        a = _lib.DensifyViewsArgs(struct_size=C.sizeof(_lib.DensifyViewsArgs), P=max_radii2D.numel(), first=int(first), count=int(count),
+                                  n_views=packets.shape[0], packets=v(packets), packet_stride_bytes=packets.shape[1] * 4,
+                                  capacity_rows=int(capacity_rows), means3D=v(means3D), scales=None if raw else v(scales),
+                                  rotations=None if raw else v(rotations), opacities=None if raw else v(opacities),
+                                  raw_opacities=v(opacities) if raw else None, raw_scales=v(scales) if raw else None,
+                                  raw_rotations=v(rotations) if raw else None, xyz_gradient_accum=v(xyz_gradient_accum), denom=v(denom),
+                                  max_radii2D=v(max_radii2D), status=v(status), status_seq=int(status_seq),
+                                  hip_stream=torch.cuda.current_stream(dev).cuda_stream)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().frg_densify_accumulate_views(C.byref(a))
+        _lib.check(rc, "frg_densify_accumulate_views")
 
     @staticmethod
     def densify_plan(raw_scales, raw_opacities, xyz_gradient_accum, denom, max_grad, min_opacity, extent, percent_dense,
@@ -95,7 +116,10 @@ class DensityControl:
     (logit)) holds: ``xyz_gradient_accum`` [P,1], ``denom`` [P,1], ``max_radii2D`` [P], float32 as the reference keeps them.
 
     ``ShardedFlatAdam`` is refused: its moments exist per shard only, and moving rows re-shards them -- not implemented.
-    Statistics over a view-parallel batch stay with ``parallel.DensificationStats``."""
+    Statistics over a view-parallel batch: hand this object to ``ViewParallelRasterizer(..., slotsum=True, densify=control)``
+    -- the slot-sum exchange then adds every view of a step from the gathered packets (``frg_densify_accumulate_views``: what
+    ``add_stats`` adds view by view, bit for bit, identical on every rank, no further collective); after
+    ``densify_and_prune`` call ``ViewParallelRasterizer.adopt_scene`` with the resized model."""
 
     def __init__(self, optimizer: FlatAdam, percent_dense: float = 0.01, binding: str = "ctypes"):
         if isinstance(optimizer, ShardedFlatAdam):

@@ -521,12 +521,14 @@ SUM_ROW_FLOATS = 12     # ... and its rows {masked dRGB[3], six pixel moments, t
 SUM_TILE = 1536         # chunk boundaries fall on whole tiles of the combine pass, whichever tile size it picks (3 .. 24 blocks of 64)
 
 
-def sum_packet_words(n: int, capacity: int) -> int:
+def sum_packet_words(n: int, capacity: int, visibility: bool = False) -> int:
     """32-bit words of a packet of n Gaussians with room for `capacity` rows (= frg_sum_packet_bytes / 4): header, one bit per
-    Gaussian, one row offset per block of 64, the rows."""
+    Gaussian, one row offset per block of 64, the rows.  visibility: and the section the densification statistics need behind
+    them -- one more bit per Gaussian (= frg_sum_packet_bytes_ex(n, capacity, 1) / 4)."""
     nblk = (n + 63) // 64
     rows_at = (SUM_HDR_WORDS + 2 * nblk + nblk + 3) // 4 * 4
-    return (rows_at + SUM_ROW_FLOATS * capacity + 3) // 4 * 4
+    words = (rows_at + SUM_ROW_FLOATS * capacity + 3) // 4 * 4
+    return (words + 2 * nblk + 3) // 4 * 4 if visibility else words
 
 
 def _hip_sum_packer(ex: "SlotSumExchange", chunk: int, dest: torch.Tensor):
@@ -537,6 +539,18 @@ def _hip_sum_packer(ex: "SlotSumExchange", chunk: int, dest: torch.Tensor):
     first, count = ex.chunks[chunk]
     cam = c["cam"]
     stream = C.c_void_p(torch.cuda.current_stream(dest.device).cuda_stream)
+    if ex.densify is not None:      # the packet also says which Gaussians the view saw (frg_pack_sum_rows_ex with the forward's radii)
+        radii = c.get("radii")
+        if radii is None or radii.numel() != ex.P:
+            raise RuntimeError("slot-sum exchange with densify: note_view() must carry the forward's radii")
+        v = lambda t: t.data_ptr()
+        a = _lib.PackSumArgs(struct_size=C.sizeof(_lib.PackSumArgs), P=ex.P, R=int(c["R"]), first=first, count=count, workspace=v(c["work"]),
+                             workspace_bytes=c["work"].numel(), drgb_masked=v(ex.own_drgb), viewmatrix=v(cam.viewmatrix), projmatrix=v(cam.projmatrix),
+                             campos=v(cam.campos), tan_fovx=float(cam.tanfovx), tan_fovy=float(cam.tanfovy), width=int(cam.image_width),
+                             height=int(cam.image_height), scale_modifier=float(c.get("scale_modifier", 1.0)), D=int(c["D"]), packet=v(dest),
+                             packet_bytes=dest.numel() * 4, capacity_rows=int(ex.capacity[chunk]), radii=v(radii), hip_stream=stream.value)
+        _lib.check(_lib.lib().frg_pack_sum_rows_ex(C.byref(a)), "frg_pack_sum_rows_ex")
+        return
     rc = _lib.lib().frg_pack_sum_rows(ex.P, int(c["R"]), first, count, _p(c["work"]), c["work"].numel(), _p(ex.own_drgb),
                                       _p(cam.viewmatrix), _p(cam.projmatrix), _p(cam.campos), float(cam.tanfovx), float(cam.tanfovy),
                                       int(cam.image_width), int(cam.image_height), float(c.get("scale_modifier", 1.0)), int(c["D"]),
@@ -568,6 +582,22 @@ def _hip_sum_combiner(ex: "SlotSumExchange", chunk: int, packets: torch.Tensor, 
     _lib.check(rc, "frg_backward_combine")
 
 
+def _hip_view_stats_accumulator(ex: "SlotSumExchange", chunk: int, packets: torch.Tensor, n_views: int, seq: int):
+    """ex.densify's statistics of chunk `chunk` += every view's share, in view order, from the gathered packets
+    (frg_densify_accumulate_views, through the binding a DensityControl was built with)."""
+    if packets.device.type != "cuda":
+        raise RuntimeError("the slot-sum exchange forms the densification statistics with a HIP kernel (no CPU path; tests inject their own)")
+    ops = getattr(ex.densify, "ops", None)
+    if ops is None or not hasattr(ops, "densify_accumulate_views"):
+        from .densify import native_ops
+        ops = native_ops("ctypes")
+    first, count = ex.chunks[chunk]
+    pr, d = ex.params, ex.densify
+    ops.densify_accumulate_views(packets[:n_views], first, count, int(ex.capacity[chunk]), pr["means3D"], pr["scales"], pr["rotations"],
+                                 pr["opacities"], bool(ex.raw_params), d.xyz_gradient_accum, d.denom, d.max_radii2D,
+                                 ex.stats_status[chunk], int(seq))
+
+
 class SlotSumExchange(GradientExchange):
     """The exchange plan of round 6: ranks all-gather the nine per-Gaussian SLOT SUMS of their view's backward (phase 1) for
     the Gaussians that have any -- 48-byte rows {masked dRGB, six moments, three view-direction terms} in index order behind a bit mask, a fixed-capacity packet per chunk of
@@ -584,12 +614,18 @@ class SlotSumExchange(GradientExchange):
         of one range runs while the next range's packets are still on the wire.
 
     Rank-local outputs of the backward (dL_dmeans2D -- the viewspace gradient --, dL_dcov3D, dL_dcolors) are NOT produced on
-    this path: phase 2 never runs for the own view alone."""
+    this path: phase 2 never runs for the own view alone.
+
+    densify (a densify.DensityControl, or any object with xyz_gradient_accum [P,1], denom [P,1], max_radii2D [P]): the packets
+    then also carry which Gaussians their view saw (one bit per Gaussian; note_view must carry the forward's `radii`), and every
+    chunk whose verdict is clean adds ALL the step's views to those statistics, in view order, exactly once
+    (frg_densify_accumulate_views) -- what DensityControl.add_stats adds view by view in one process, bit for bit, the same on
+    every rank, with no further collective.  Without it nothing changes: the same packets, byte for byte."""
 
     slotsum = True
 
     def __init__(self, shapes: dict, device, process_group=None, average: bool = False, chunks: int = 2, slack: float = 1.125,
-                 packer=None, combiner=None, raw_params: bool = False):
+                 packer=None, combiner=None, raw_params: bool = False, densify=None, accumulator=None):
         super().__init__(shapes, device, process_group, average)
         if "shs" not in self.shapes:
             raise ValueError("the slot-sum exchange needs the SH parameterisation (shs)")
@@ -606,9 +642,14 @@ class SlotSumExchange(GradientExchange):
         self.slack = float(slack)
         self.packer = packer or _hip_sum_packer
         self.combiner = combiner or _hip_sum_combiner
+        self.densify = densify
+        self.accumulator = accumulator or _hip_view_stats_accumulator
         pin = self.device.type == "cuda"
         # the combine pass's verdict per chunk: 64-bit words (sequence number << 32 | value) -- [0] overflow, [1 + v] rows view v wanted
         self.status = [torch.zeros(1 + 16, dtype=torch.int64, pin_memory=pin) for _ in self.chunks]
+        # the statistics pass's own word per chunk (sequence number << 32 | 1 = refused: nothing written)
+        self.stats_status = [torch.zeros(1, dtype=torch.int64, pin_memory=pin) for _ in self.chunks]
+        self.stats_seq = [0] * len(self.chunks)
         self.seq = 0
         self.packet_own = [None] * len(self.chunks)
         self.packets_all = [None] * len(self.chunks)
@@ -627,19 +668,20 @@ class SlotSumExchange(GradientExchange):
         self.params = params
 
     def note_view(self, **ctx):
-        """What the packer needs of the backward that just ran its phase 1: P-sized workspace `work`, R, cam, D, scale_modifier."""
+        """What the packer needs of the backward that just ran its phase 1: P-sized workspace `work`, R, cam, D, scale_modifier
+        -- and, with densify, the forward's `radii`."""
         self.view_ctx = ctx
 
     @property
     def wire_floats_per_rank(self) -> int:
-        return sum(sum_packet_words(n, cap) for (_, n), cap in zip(self.chunks, self.capacity))
+        return sum(sum_packet_words(n, cap, self.densify is not None) for (_, n), cap in zip(self.chunks, self.capacity))
 
     def _world(self):
         import torch.distributed as dist
         return dist.get_world_size(self.group)
 
     def _ensure(self, c: int, world: int):
-        words = sum_packet_words(self.chunks[c][1], self.capacity[c])
+        words = sum_packet_words(self.chunks[c][1], self.capacity[c], self.densify is not None)
         if self.packet_own[c] is None or self.packet_own[c].numel() != words:
             self.packet_own[c] = torch.zeros(words, dtype=torch.int32, device=self.device)
         if self.packets_all[c] is None or tuple(self.packets_all[c].shape) != (world, words):
@@ -676,6 +718,22 @@ class SlotSumExchange(GradientExchange):
         self.stats["packet_bytes"] = 4 * self.wire_floats_per_rank
         return self._works[-1]
 
+    def _accumulate(self, c: int, world: int):
+        """With densify: chunk c's packets (verdict clean, capacity still the one they were packed with) -> the statistics."""
+        d = self.densify
+        if d is None:
+            return
+        if d.max_radii2D.numel() != self.P:
+            raise RuntimeError(f"slot-sum exchange: the statistics hold {d.max_radii2D.numel()} Gaussians, the exchange {self.P}: "
+                               "ViewParallelRasterizer.adopt_scene() after densify_and_prune")
+        if self.stats_seq[c]:       # the last pass over this chunk must not have refused its packets (no wait: read if posted)
+            w = int(self.stats_status[c][0])
+            if (w >> 32) == self.stats_seq[c] and (w & 0xffffffff):
+                raise RuntimeError(f"slot-sum exchange: the statistics pass refused chunk {c}'s packets (no visibility section, another "
+                                   "range, or an overflow the combine pass did not report)")
+        self.stats_seq[c] = self.stats_seq[c] % 0x7fffffff + 1
+        self.accumulator(self, c, self.packets_all[c], world, self.stats_seq[c])
+
     def _finish_on_current_stream(self):
         import torch.distributed as dist
         if self.params is None:
@@ -701,7 +759,9 @@ class SlotSumExchange(GradientExchange):
                 over2, counts = self._verdict(c, world)
                 if over2:
                     raise RuntimeError(f"slot-sum exchange: chunk {c} still overflows a capacity of {self.capacity[c]} rows (wanted {max(counts)})")
+                self._accumulate(c, world)      # once, from the packets that fit
             else:            # the next step's packets: what this step's views wanted, with slack (shrinks only by a clear margin)
+                self._accumulate(c, world)      # (before the capacity moves: the pass checks the packets against it)
                 want = min(self.chunks[c][1], (int(max(counts) * self.slack) // 256 + 1) * 256)
                 if want < 0.8 * self.capacity[c] or want > self.capacity[c]:
                     self.capacity[c] = want
@@ -756,11 +816,16 @@ class SlotSumExchange(GradientExchange):
             self.packer(self, c, self.packets_all[c][view_index])
 
     def combine_local(self, world: int):
-        """The combine pass over `world` locally packed views -> [(overflow?, rows wanted per view)] per chunk."""
+        """The combine pass over `world` locally packed views -> [(overflow?, rows wanted per view)] per chunk.  With densify, the
+        chunks whose verdict is clean add their views to the statistics."""
         self.seq = self.seq % 0x7fffffff + 1
         for c in range(len(self.chunks)):
             self.combiner(self, c, self.packets_all[c], world, self.seq)
-        return [self._verdict(c, world) for c in range(len(self.chunks))]
+        verdicts = [self._verdict(c, world) for c in range(len(self.chunks))]
+        for c, (over, _) in enumerate(verdicts):
+            if not over:
+                self._accumulate(c, world)
+        return verdicts
 
     def wait_on_side_stream(self):
         if self._works:
@@ -813,7 +878,10 @@ class DensificationStats:
         xyz_gradient_accum += sum over visible views of ||viewspace_grad[:, :2]||
         denom              += number of views in which the Gaussian was visible
     i.e. ONE all-reduce(MAX) of P int32 and ONE all-reduce(SUM) of 2 P floats.  Frosting's
-    refinement does not densify (refine.py has no such step), so this is optional on the C5 path."""
+    refinement does not densify (refine.py has no such step), so this is optional on the C5 path.
+    It needs an exchange plan whose backward WRITES the viewspace gradient (allreduce, factored, sparse).  The slot-sum plan does
+    not (its phase 2 never runs for the own view alone: ViewParallelRasterizer.dL_dmeans2D stays zero there) -- that plan keeps
+    the statistics itself, from its packets: ViewParallelRasterizer(..., slotsum=True, densify=...)."""
 
     def __init__(self, P: int, device, process_group=None):
         self.group = process_group
@@ -848,10 +916,12 @@ class ViewParallelRasterizer:
     def __init__(self, scene, device, process_group=None, average: bool = False, factor_sh: bool = False,
                  deferred_counters: bool = False, capacity_slack: float = 1.25, reduce: str = "allreduce",
                  write_all_outputs: bool = True, raw_params: bool = False, sparse: bool = False, live_rows: bool = False,
-                 slotsum: bool = False, chunks: int = 2, phase1_in_pieces: bool = False):
+                 slotsum: bool = False, chunks: int = 2, phase1_in_pieces: bool = False, densify=None):
         """deferred_counters: after the first (synchronous) view, forwards run through
         frg_forward_deferred -- no host synchronisation inside the step; finish() then reports the
-        true instance count and whether the view has to be repeated (capacity exceeded)."""
+        true instance count and whether the view has to be repeated (capacity exceeded).
+        densify (slot-sum plan only): a densify.DensityControl, or any object with its three statistic tensors -- the exchange
+        adds every view of a step to them (SlotSumExchange)."""
         self.dev = torch.device(device)
         # raw_params: scene.opacities / scales / rotations hold the model's RAW parameters (logit, log, unnormalised
         # quaternion); the activations run inside the per-Gaussian kernels (frg_forward_ex / frg_backward_ex) and the
@@ -878,30 +948,42 @@ class ViewParallelRasterizer:
         # sparse: the exchange moves rows of the Gaussians with a gradient (GradientExchange, third plan)
         # slotsum: the ranks exchange the slot sums of phase 1 and every rank runs phase 2 for every view (SlotSumExchange, round 6)
         self._chunks = chunks
-        self.exchanges = [self._make_exchange(shapes, "slotsum" if slotsum else "sparse" if sparse else "factored" if factor_sh else "allreduce", reduce)
-                          for _ in range(2)]
+        if densify is not None and not slotsum:
+            raise ValueError("densify: the statistics come from the slot-sum packets (slotsum=True); the other plans write dL_dmeans2D "
+                             "(DensityControl.add_stats, DensificationStats)")
+        self._densify = densify
+        self._fwd_gen = 0
+        self._plan = ("slotsum" if slotsum else "sparse" if sparse else "factored" if factor_sh else "allreduce", reduce)
+        self.exchanges = [self._make_exchange(shapes, *self._plan) for _ in range(2)]
         self.exchange = self.exchanges[0]
-        f = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)
-        # rank-local (not exchanged) backward outputs.  dL_dcov3D is an intermediate of the chain when the covariance
-        # comes from scales / rotations, but it is one of the eight tensors the reference's backward returns
-        # (rasterize_points.cu:195) and part of SURVEY 8(d)'s byte model (24 of the 284 B per Gaussian): written unless
-        # the caller opts out (write_all_outputs=False)
-        self.dL_dmeans2D, self.dL_dcolors = f(P, 3), f(P, 3)
         self.write_all_outputs = write_all_outputs
-        self.dL_dcov3D = f(P, 6) if write_all_outputs else None
+        self._alloc_rank_local()
         self.geom, self.binning, self.img, self.work = (_lib.Scratch(self.dev, 1.25) for _ in range(4))
-        self.radii = torch.empty(P, dtype=torch.int32, device=self.dev)
-        self.row_live = torch.zeros(P, dtype=torch.uint8, device=self.dev) if live_rows else None
         if live_rows and process_group is not None:
             raise ValueError("live_rows leaves the rows of Gaussians without a gradient unwritten: not with a gradient exchange")
         self.out_color = None
         self.num_rendered = 0
         self._view = None
 
+    def _alloc_rank_local(self):
+        """The P-sized buffers beside the exchanges."""
+        P = self.P
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)
+        # rank-local (not exchanged) backward outputs.  dL_dcov3D is an intermediate of the chain when the covariance
+        # comes from scales / rotations, but it is one of the eight tensors the reference's backward returns
+        # (rasterize_points.cu:195) and part of SURVEY 8(d)'s byte model (24 of the 284 B per Gaussian): written unless
+        # the caller opts out (write_all_outputs=False)
+        # (dL_dmeans2D zeroed: the slot-sum plan's backward never writes it, and a reader must not meet uninitialised memory)
+        self.dL_dmeans2D, self.dL_dcolors = torch.zeros((P, 3), dtype=torch.float32, device=self.dev), f(P, 3)
+        self.dL_dcov3D = f(P, 6) if self.write_all_outputs else None
+        self.radii = torch.empty(P, dtype=torch.int32, device=self.dev)
+        self.row_live = torch.zeros(P, dtype=torch.uint8, device=self.dev) if self.live_rows else None
+
     def _make_exchange(self, shapes, plan: str, reduce: str):
         s = self.scene
         if plan == "slotsum":
-            ex = SlotSumExchange(shapes, self.dev, self._group, self._average, chunks=self._chunks, raw_params=self.raw_params)
+            ex = SlotSumExchange(shapes, self.dev, self._group, self._average, chunks=self._chunks, raw_params=self.raw_params,
+                                 densify=self._densify)
             ex.set_params(dict(means3D=s.means3D, shs=s.shs, scales=s.scales, rotations=s.rotations, opacities=s.opacities))
             return ex
         ex = GradientExchange(shapes, self.dev, self._group, self._average, factor_sh=(plan != "allreduce"), reduce=reduce,
@@ -918,8 +1000,42 @@ class ViewParallelRasterizer:
         reduce = reduce or old.reduce
         self.exchanges = None
         del old
+        if self._densify is not None and plan != "slotsum":
+            raise ValueError("densify: the statistics come from the slot-sum packets; this rasterizer was built with densify")
+        self._plan = (plan, reduce)
         self.exchanges = [self._make_exchange(shapes, plan, reduce) for _ in range(2)]
         self.exchange = self.exchanges[0]
+
+    def adopt_scene(self, scene):
+        """Carry on with a RESIZED model: `scene` holds the parameters after DensityControl.densify_and_prune / FlatAdam.adopt
+        (views of the optimizer's new buffers, or copies).  The exchanges are made anew for the new P -- the same plan; the
+        slot-sum packets' capacity back to "room for every Gaussian", the gradient buffers zeroed -- and so are the P-sized
+        buffers beside them (radii, dL_dmeans2D, dL_dcolors, dL_dcov3D, row_live); the scratch arenas and the instance capacity
+        stay.  No exchange may be pending and no deferred forward unfinished.
+        With a process group: collective -- ONE all-reduce (the minimum and the maximum of the ranks' new P), and a RuntimeError
+        on every rank if they disagree.  They cannot disagree when every rank densifies the same statistics (the slot-sum
+        plan's are identical on every rank) and seeds densify_and_prune's generator alike (or passes the same `noise`): the
+        plan is then the same everywhere."""
+        import torch.distributed as dist
+        if self._pending or any(ex._works or getattr(ex, "_joined", None) is not None for ex in self.exchanges):
+            raise RuntimeError("adopt_scene: an exchange (or a deferred forward) is still pending: wait for it first")
+        P, K = int(scene.means3D.shape[0]), int(scene.shs.shape[1])
+        if K != self.K:
+            raise ValueError(f"adopt_scene: {K} SH coefficients, the rasterizer was built for {self.K}")
+        if self._group is not None and dist.is_initialized():
+            t = torch.tensor([P, -P], dtype=torch.int64, device=self.dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self._group)
+            hi, lo = int(t[0]), -int(t[1])
+            if hi != lo:
+                raise RuntimeError(f"adopt_scene: the ranks hold models of {lo} .. {hi} Gaussians (this one {P}): every rank must seed "
+                                   "densify_and_prune's generator alike")
+        self.scene, self.P = scene, P
+        shapes = dict(means3D=(P, 3), scales=(P, 3), rotations=(P, 4), opacities=(P, 1), shs=(P, K, 3))
+        self.exchanges = None
+        self.exchanges = [self._make_exchange(shapes, *self._plan) for _ in range(2)]
+        self.exchange = self.exchanges[0]
+        self._alloc_rank_local()
+        self._view = None
 
     def forward(self, cam, bg, deferred=None, keep_mask=None, forward_only=False):
         """Render one view.  With deferred counters the returned image is valid only if the
@@ -961,6 +1077,7 @@ class ViewParallelRasterizer:
             if self.deferred_counters:
                 self.capacity = max(self.capacity, int(rc * self.capacity_slack) + 4096)
         self._view = (cam, bg)
+        self._fwd_gen += 1
         return self.out_color, self.radii
 
     def finish(self) -> bool:
@@ -1037,9 +1154,10 @@ class ViewParallelRasterizer:
             range_first=0 if sum_range is None else int(sum_range[0]), range_count=0 if sum_range is None else int(sum_range[1]))
         _lib.check(L.frg_backward_ex(C.byref(a)), "frg_backward")
         if slot_sums:
-            gen = self._bwd_gen
-            ex.note_view(work=work, R=self.num_rendered, cam=cam, D=s.sh_degree, scale_modifier=1.0,
-                         intact=lambda: self._bwd_gen == gen)
+            gen, fgen = self._bwd_gen, self._fwd_gen
+            # (with densify a repack also reads this forward's radii: a later forward has overwritten them)
+            ex.note_view(work=work, R=self.num_rendered, cam=cam, D=s.sh_degree, scale_modifier=1.0, radii=self.radii,
+                         intact=lambda: self._bwd_gen == gen and (self._densify is None or self._fwd_gen == fgen))
             return g
         if phase == 2:
             return g              # (the payload left with phase 1)

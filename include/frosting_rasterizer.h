@@ -458,12 +458,37 @@ int frg_scatter_grad_rows(long long n_rows, int P, const float* rows, float* dL_
  *                         status_seq << 32 | value): word 0 <- 1 if any packet overflowed its capacity or does not describe
  *                         this range, word 1 + v <- the rows view v wanted.  A host polling pinned memory until every word
  *                         carries status_seq learns the verdict while the pass runs, without synchronising the stream (the
- *                         pass's first workgroup posts it as it starts).  On overflow the outputs are incomplete. */
+ *                         pass's first workgroup posts it as it starts).  On overflow the outputs are incomplete.
+ *   frg_pack_sum_rows_ex  (addition to version 2: look the symbol up) frg_pack_sum_rows with its arguments in one record, plus
+ *                         `radii` (int32 [P] of the forward whose backward left the workspace; NULL: exactly frg_pack_sum_rows,
+ *                         byte for byte).  With radii the packet gains a VISIBILITY SECTION behind its rows, 16-byte aligned:
+ *                         one uint64 per block of 64 Gaussians, bit g % 64 of word g / 64 = radii[first + g] > 0, and header
+ *                         word 6 holds the section's offset in 32-bit words (0: the packet has none).  Such a packet has
+ *                         frg_sum_packet_bytes_ex(count, capacity_rows, 1) bytes.  frg_backward_combine ignores the section;
+ *                         frg_densify_accumulate_views needs it. */
 size_t frg_sum_packet_bytes(int n_gaussians, long long capacity_rows);
+size_t frg_sum_packet_bytes_ex(int n_gaussians, long long capacity_rows, int with_visibility);
 int frg_pack_sum_rows(int P, int R, int first, int count, char* workspace, size_t workspace_bytes, const float* drgb_masked,
                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
                       int width, int height, float scale_modifier, int D, void* packet, size_t packet_bytes, long long capacity_rows,
                       void* hip_stream);
+typedef struct frg_pack_sum_args {
+    size_t struct_size;
+    int P, R, first, count;
+    char* workspace;
+    size_t workspace_bytes;
+    const float *drgb_masked, *viewmatrix, *projmatrix, *campos;
+    float tan_fovx, tan_fovy;
+    int width, height;
+    float scale_modifier;
+    int D;
+    void* packet;
+    size_t packet_bytes;
+    long long capacity_rows;
+    const int* radii;             /* optional: the packet gets its visibility section */
+    void* hip_stream;
+} frg_pack_sum_args;
+int frg_pack_sum_rows_ex(const frg_pack_sum_args* args);
 typedef struct frg_combine_args {
     size_t struct_size;
     int P, first, count, n_views;
@@ -584,6 +609,32 @@ int frg_photometric_loss(int channels, int width, int height, const float* image
  * Gaussian was never written -- it is zero and is not read. */
 int frg_densify_accumulate(int P, const int* radii, const float* dL_dmean2D, const unsigned char* row_live,
                            float* xyz_gradient_accum, float* denom, float* max_radii2D, void* hip_stream);
+
+/* frg_densify_accumulate_views: the statistics of EVERY view of a view-parallel step from the gathered slot-sum packets of
+ * Gaussians [first, first + count) (frg_pack_sum_rows_ex with radii: packets + v * packet_stride_bytes, as an all-gather leaves
+ * them, and as frg_backward_combine takes them) -- what n_views calls of frg_densify_accumulate, in view order, add on the
+ * views' own radii and dL_dmean2D, bit for bit, without either tensor: a view's visibility section says where denom += 1 and
+ * max_radii2D = max(max_radii2D, radius) apply, the radius being recomputed from the parameters and the packet's camera with
+ * the forward's expressions; where the Gaussian also has a row, dL_dmean2D.xy comes from the row's two pixel moments as in
+ * frg_backward_combine, elsewhere it is zero.  Parameters as in frg_combine_args, raw forms included.  Each statistic is read
+ * and written once per Gaussian some view saw; identical on every rank, no collective.
+ * If ANY of the packets has no visibility section, describes another range or capacity, or overflowed (rows wanted >
+ * capacity), the launch writes NOTHING to the statistics.  status (optional; device or pinned host memory, ONE 64-bit word
+ * written at once as status_seq << 32 | value): 1 = refused for that reason, 0 = accumulated.  More than 16 views: FRG_EINVAL. */
+typedef struct frg_densify_views_args {
+    size_t struct_size;
+    int P, first, count, n_views;
+    const void* packets;
+    size_t packet_stride_bytes;
+    long long capacity_rows;
+    const float *means3D, *scales, *rotations, *opacities;
+    const float *raw_opacities, *raw_scales, *raw_rotations;
+    float *xyz_gradient_accum, *denom, *max_radii2D;
+    unsigned long long* status;
+    unsigned int status_seq;
+    void* hip_stream;
+} frg_densify_views_args;
+int frg_densify_accumulate_views(const frg_densify_views_args* args);
 
 /* The thresholds of densify_and_prune(max_grad, min_opacity, extent, max_screen_size) (gaussian_model.py:389) and the
  * model's percent_dense.  prune_big_points = "max_screen_size is given": the reference's final prune then also drops
