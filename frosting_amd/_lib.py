@@ -301,6 +301,11 @@ def lib():
     L.frg_knn_workspace_bytes.argtypes = [i]
     L.frg_knn_mean_dist2.restype = i
     L.frg_knn_mean_dist2.argtypes = [i, vp, vp, vp, sz, vp]
+    if hasattr(L, "frg_knn_points"):              # (absent from an older library loaded through FROSTING_LIB for an A/B)
+        L.frg_knn_points_workspace_bytes.restype = sz
+        L.frg_knn_points_workspace_bytes.argtypes = [i, i, i]
+        L.frg_knn_points.restype = i
+        L.frg_knn_points.argtypes = [i, vp, i, vp, i, vp, vp, vp, sz, vp]
     L.frg_shell_points.restype = i
     L.frg_shell_points.argtypes = [i, vp, vp, vp, vp, vp]
     L.frg_shell_points_backward.restype = i
@@ -435,4 +440,5 @@ EXPORTED_SYMBOLS = [
     "frg_knn_workspace_bytes", "frg_knn_mean_dist2", "frg_shell_points", "frg_shell_points_backward",
     "frg_densify_accumulate", "frg_densify_workspace_bytes", "frg_densify_plan", "frg_densify_apply", "frg_reset_opacity",
     "frg_sum_packet_bytes_ex", "frg_pack_sum_rows_ex", "frg_densify_accumulate_views",
+    "frg_knn_points_workspace_bytes", "frg_knn_points",
 ]

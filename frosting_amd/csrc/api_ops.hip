@@ -337,6 +337,32 @@ int frg_knn_mean_dist2(int P, const float* points, float* mean_dist2, char* work
     return FRG_OK;
 }
 
+size_t frg_knn_points_workspace_bytes(int P1, int P2, int K)
+{
+    return P2 > 0 && P1 >= 0 ? frg::knn_points_workspace_bytes(P1, P2, K) : 0;
+}
+
+int frg_knn_points(int P1, const float* p1, int P2, const float* p2, int K, float* dists, long long* idx, char* workspace,
+                   size_t workspace_bytes, void* hip_stream)
+{
+    if (P1 < 0 || P2 < 0) return fail(FRG_EINVAL, "P1 = %d or P2 = %d < 0", P1, P2);
+    if (K < 1 || K > FRG_KNN_MAX_K) return fail(FRG_EINVAL, "K = %d outside 1 ... %d", K, FRG_KNN_MAX_K);
+    if (P1 == 0) return FRG_OK;
+    if (!p1 || !dists || !idx) return fail(FRG_EINVAL, "null pointer");
+    if (P2 == 0) {                                       // nothing to find: every slot is padding
+        FRG_HIP(hipMemsetAsync(dists, 0, (size_t)P1 * K * sizeof(float), (hipStream_t)hip_stream));
+        FRG_HIP(hipMemsetAsync(idx, 0, (size_t)P1 * K * sizeof(long long), (hipStream_t)hip_stream));
+        return FRG_OK;
+    }
+    if (!p2) return fail(FRG_EINVAL, "null pointer");
+    const bool self = p1 == p2 && P1 == P2;
+    const size_t need = frg_knn_points_workspace_bytes(self ? 0 : P1, P2, K);
+    if (!workspace || workspace_bytes < need) return fail(FRG_EALLOC, "workspace too small: need %zu bytes", need);
+    if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return fail(FRG_EINVAL, "workspace must be 256-byte aligned");
+    FRG_HIP(frg::launch_knn_points(P1, p1, P2, p2, K, self, dists, idx, workspace, (hipStream_t)hip_stream));
+    return FRG_OK;
+}
+
 int frg_shell_points(int P, const float* bary_logits, const float* cell_verts, const long long* point_cell_indices,
                      float* points, void* hip_stream)
 {

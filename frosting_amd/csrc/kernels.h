@@ -206,6 +206,11 @@ hipError_t launch_activate_bwd(int P, const float* opacity, const float* scale, 
 // 3-nearest-neighbour mean squared distance (knn.hip)
 size_t knn_workspace_bytes(int P);
 hipError_t launch_knn(int P, const float* pts, float* out, char* workspace, hipStream_t s);
+// K nearest points of p2 [P2,3] for every point of p1 [P1,3], ascending by (squared distance, index in p2); K <= 32.
+// self: p1 is p2 (its order is reused; the workspace is then sized with P1 = 0).  Slots beyond P2 hold 0 / 0.
+size_t knn_points_workspace_bytes(int P1, int P2, int K);
+hipError_t launch_knn_points(int P1, const float* p1, int P2, const float* p2, int K, bool self, float* dists, long long* idx,
+                             char* workspace, hipStream_t s);
 
 // adaptive density control over the flat parameter layout (densify.hip)
 #ifndef FRG_DENSIFY_MAX_GROUPS

@@ -538,6 +538,22 @@ size_t frg_knn_workspace_bytes(int P);
 int frg_knn_mean_dist2(int P, const float* points, float* mean_dist2, char* workspace, size_t workspace_bytes,
                        void* hip_stream);
 
+/* ---- K nearest neighbours between two point sets ---------------------------------------------
+ * pytorch3d.ops.knn_points for one batch element (callers frosting_scene/frosting_model.py:300,520,...,
+ * sugar_model.py:49,...,1059, coarse_shell.py:40,532): for every point of p1 ([P1,3] float32) the K nearest
+ * points of p2 ([P2,3] float32), 1 <= K <= FRG_KNN_MAX_K.  dists [P1,K] float32 is the squared distance
+ * (dx*dx + dy*dy) + dz*dz with d = p1 - p2, in float32 without contraction; idx [P1,K] int64 the row in p2.
+ * The K neighbours are ordered ascending by (distance, index): equal distances resolve to the smaller index
+ * (pytorch3d leaves ties open; this rule makes the value fully specified).  Nothing is excluded: when
+ * p1 == p2 && P1 == P2 (a self-query, which reuses the set's order) every point finds itself at distance 0.
+ * Slots beyond P2 (K > P2, P2 == 0 included) hold dists = 0, idx = 0, pytorch3d's padding.  Exact search.
+ * The workspace (256-byte aligned) is sized by frg_knn_points_workspace_bytes(P1, P2, K); a self-query
+ * needs only frg_knn_points_workspace_bytes(0, P2, K). */
+#define FRG_KNN_MAX_K 32
+size_t frg_knn_points_workspace_bytes(int P1, int P2, int K);
+int frg_knn_points(int P1, const float* p1, int P2, const float* p2, int K, float* dists, long long* idx,
+                   char* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- Frosting shell parameterisation of the centres -------------------------------------------
  * The rest of SURVEY.md 8(f) rank 3.  points = sum_k softmax(bary_logits)[k] * cell_verts[cell][k]
  * (frosting_scene/frosting_model.py:713-724; cell_verts [F,6,3] = shell_cells_verts.reshape(-1, 6, 3),
