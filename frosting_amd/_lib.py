@@ -162,6 +162,26 @@ class DensifyParams(C.Structure):
                 ("prune_big_points", C.c_int)]
 
 
+class FieldArgs(C.Structure):
+    """frg_field_args (include/frosting_rasterizer.h)."""
+    _fields_ = [("struct_size", C.c_size_t),
+                ("P", C.c_int), ("N", C.c_int), ("K", C.c_int),
+                ("idx_is_int64", C.c_int),
+                ("idx", C.c_void_p),
+                ("x", C.c_void_p), ("points", C.c_void_p), ("scaling", C.c_void_p), ("quaternions", C.c_void_p), ("strengths", C.c_void_p),
+                ("beta_mode", C.c_int),
+                ("flags", C.c_int),
+                ("density_threshold", C.c_double), ("density_factor", C.c_double), ("opacity_min_clamp", C.c_double),
+                ("beta_fallback", C.c_void_p),
+                ("density", C.c_void_p), ("opacities", C.c_void_p), ("beta", C.c_void_p), ("sdf", C.c_void_p),
+                ("dL_ddensity", C.c_void_p), ("dL_dopacities", C.c_void_p), ("dL_dbeta", C.c_void_p), ("dL_dsdf", C.c_void_p),
+                ("dL_dx", C.c_void_p), ("dL_dpoints", C.c_void_p), ("dL_dscaling", C.c_void_p), ("dL_dquaternions", C.c_void_p),
+                ("dL_dstrengths", C.c_void_p),
+                ("bad_index", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("hip_stream", C.c_void_p)]
+
+
 # The parameters of the reference-shaped entry points are fields of the structs: their positional order, written once.
 # (argtypes of the functions and the arguments of a call are both derived from it.)
 FORWARD_POSITIONAL = [name for name, _ in ForwardArgs._fields_[1:ForwardArgs._fields_.index(("hip_stream", C.c_void_p)) + 1]]
@@ -386,6 +406,13 @@ def lib():
         L.frg_pack_sum_rows_ex.argtypes = [C.POINTER(PackSumArgs)]
         L.frg_densify_accumulate_views.restype = i
         L.frg_densify_accumulate_views.argtypes = [C.POINTER(DensifyViewsArgs)]
+    if hasattr(L, "frg_field_forward"):           # (absent from an older library loaded through FROSTING_LIB for an A/B)
+        L.frg_field_workspace_bytes.restype = sz
+        L.frg_field_workspace_bytes.argtypes = [i, i, i, i]
+        L.frg_field_forward.restype = i
+        L.frg_field_forward.argtypes = [C.POINTER(FieldArgs)]
+        L.frg_field_backward.restype = i
+        L.frg_field_backward.argtypes = [C.POINTER(FieldArgs)]
     _lib = L
     return L
 
@@ -441,4 +468,5 @@ EXPORTED_SYMBOLS = [
     "frg_densify_accumulate", "frg_densify_workspace_bytes", "frg_densify_plan", "frg_densify_apply", "frg_reset_opacity",
     "frg_sum_packet_bytes_ex", "frg_pack_sum_rows_ex", "frg_densify_accumulate_views",
     "frg_knn_points_workspace_bytes", "frg_knn_points",
+    "frg_field_workspace_bytes", "frg_field_forward", "frg_field_backward",
 ]

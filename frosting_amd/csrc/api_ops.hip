@@ -491,4 +491,65 @@ int frg_reset_opacity(int P, float* raw_opacities, float* exp_avg, float* exp_av
     return FRG_OK;
 }
 
+// ---- density / SDF field over K neighbour Gaussians (field.hip) ----
+size_t frg_field_workspace_bytes(int P, int N, int K, int flags)
+{
+    if (P <= 0 || N <= 0 || K < 1 || K > FRG_KNN_MAX_K) return 0;
+    return frg::field_workspace_bytes(P, N, K, (flags & FRG_FIELD_BACKWARD) != 0);
+}
+
+static int field_call(const frg_field_args* a, bool backward)
+{
+    const char* what = backward ? "frg_field_backward" : "frg_field_forward";
+    if (!a || a->struct_size != sizeof(frg_field_args))
+        return fail(FRG_EINVAL, "frg_field_args: struct_size %zu, this library expects %zu", a ? a->struct_size : (size_t)0, sizeof(frg_field_args));
+    if (a->K < 1 || a->K > FRG_KNN_MAX_K) return fail(FRG_EINVAL, "%s: K = %d outside 1 ... %d", what, a->K, FRG_KNN_MAX_K);
+    if (a->P < 0 || a->N < 0) return fail(FRG_EINVAL, "%s: P = %d or N = %d < 0", what, a->P, a->N);
+    if ((long long)a->N * 32 > 0x7fffffffLL) return fail(FRG_EINVAL, "%s: N = %d: 32 N must stay below 2^31", what, a->N);
+    if (a->beta_mode != FRG_FIELD_BETA_NONE && a->beta_mode != FRG_FIELD_BETA_AVERAGE && a->beta_mode != FRG_FIELD_BETA_WEIGHTED)
+        return fail(FRG_EINVAL, "%s: unknown beta_mode %d", what, a->beta_mode);
+    if (a->beta_mode == FRG_FIELD_BETA_NONE && (a->beta || a->sdf || a->dL_dbeta || a->dL_dsdf))
+        return fail(FRG_EINVAL, "%s: beta and sdf need a beta_mode", what);
+    if (a->N > 0 && a->P == 0) return fail(FRG_EINVAL, "%s: samples without Gaussians", what);
+    if (a->N > 0 && (!a->idx || !a->x || !a->bad_index)) return fail(FRG_EINVAL, "%s: null pointer (idx, x, bad_index)", what);
+    if (a->P > 0 && (!a->points || !a->scaling || !a->quaternions || !a->strengths)) return fail(FRG_EINVAL, "%s: null pointer (points, scaling, quaternions, strengths)", what);
+    if (a->beta_mode == FRG_FIELD_BETA_WEIGHTED && !a->beta_fallback) return fail(FRG_EINVAL, "%s: null pointer (beta_fallback of the weighted average)", what);
+    if (backward && ((a->N > 0 && !a->dL_dx) || (a->P > 0 && (!a->dL_dpoints || !a->dL_dscaling || !a->dL_dquaternions || !a->dL_dstrengths))))
+        return fail(FRG_EINVAL, "%s: null gradient output", what);
+    if ((reinterpret_cast<uintptr_t>(a->quaternions) | reinterpret_cast<uintptr_t>(a->dL_dquaternions)) % 16 != 0)
+        return fail(FRG_EINVAL, "%s: quaternions and dL_dquaternions must be 16-byte aligned", what);
+    hipStream_t s = (hipStream_t)a->hip_stream;
+    if (a->N == 0) {                                       // no pair names anybody: every Gaussian's rows are zeros
+        if (backward && a->P > 0) {
+            FRG_HIP(hipMemsetAsync(a->dL_dpoints, 0, (size_t)a->P * 12, s));
+            FRG_HIP(hipMemsetAsync(a->dL_dscaling, 0, (size_t)a->P * 12, s));
+            FRG_HIP(hipMemsetAsync(a->dL_dquaternions, 0, (size_t)a->P * 16, s));
+            FRG_HIP(hipMemsetAsync(a->dL_dstrengths, 0, (size_t)a->P * 4, s));
+        }
+        return FRG_OK;
+    }
+    const size_t need = frg::field_workspace_bytes(a->P, a->N, a->K, backward);
+    if (!a->workspace || a->workspace_bytes < need) return fail(FRG_EINVAL, "%s: workspace too small: need %zu bytes", what, need);
+    if (reinterpret_cast<uintptr_t>(a->workspace) % 256 != 0) return fail(FRG_EINVAL, "%s: workspace must be 256-byte aligned", what);
+    frg::FieldLaunch p{};
+    p.P = a->P; p.N = a->N; p.K = a->K; p.idx64 = a->idx_is_int64 ? 1 : 0; p.beta_mode = a->beta_mode;
+    p.recompute = (a->flags & FRG_FIELD_RECOMPUTE) ? 1 : 0;
+    p.idx = a->idx; p.x = a->x; p.points = a->points; p.scaling = a->scaling; p.quaternions = a->quaternions; p.strengths = a->strengths;
+    // the reference's Python floats: formed in double, rounded once where a float32 tensor op takes them
+    p.density_factor = a->density_factor;
+    p.sdf_offset = std::sqrt(-2.0 * std::log(std::fmin(a->density_threshold, 1.0)));
+    p.opacity_min_clamp = a->opacity_min_clamp;
+    p.beta_fallback = a->beta_fallback;
+    p.density = a->density; p.opacities = a->opacities; p.beta = a->beta; p.sdf = a->sdf;
+    p.g_density = a->dL_ddensity; p.g_opacities = a->dL_dopacities; p.g_beta = a->dL_dbeta; p.g_sdf = a->dL_dsdf;
+    p.dL_dx = a->dL_dx; p.dL_dpoints = a->dL_dpoints; p.dL_dscaling = a->dL_dscaling; p.dL_dquaternions = a->dL_dquaternions;
+    p.dL_dstrengths = a->dL_dstrengths;
+    p.bad_index = a->bad_index;
+    FRG_HIP(frg::launch_field(p, backward, a->workspace, s));
+    return FRG_OK;
+}
+
+int frg_field_forward(const frg_field_args* a) { return field_call(a, false); }
+int frg_field_backward(const frg_field_args* a) { return field_call(a, true); }
+
 }  // extern "C"

@@ -212,6 +212,25 @@ size_t knn_points_workspace_bytes(int P1, int P2, int K);
 hipError_t launch_knn_points(int P1, const float* p1, int P2, const float* p2, int K, bool self, float* dists, long long* idx,
                              char* workspace, hipStream_t s);
 
+// density / SDF field over K neighbour Gaussians (field.hip).  One record for the pack, pair, list-walk and hub kernels; the
+// workspace pointers are filled by launch_field.
+struct FieldLaunch {
+    int P, N, K, idx64, beta_mode, recompute;
+    const void* idx;
+    const float *x, *points, *scaling, *quaternions, *strengths;
+    double density_factor, sdf_offset, opacity_min_clamp;       // the forward rounds them to float32 once, the backward does not
+    const float* beta_fallback;
+    float *density, *opacities, *beta, *sdf;
+    const float *g_density, *g_opacities, *g_beta, *g_sdf;
+    float *dL_dx, *dL_dpoints, *dL_dscaling, *dL_dquaternions, *dL_dstrengths;
+    int* bad_index;
+    float4* rec;
+    double2* ab;
+    uint32_t *keys, *keys_s, *vals_s, *seg_begin, *seg_end;
+};
+size_t field_workspace_bytes(int P, int N, int K, bool backward);
+hipError_t launch_field(FieldLaunch p, bool backward, char* workspace, hipStream_t s);
+
 // adaptive density control over the flat parameter layout (densify.hip)
 #ifndef FRG_DENSIFY_MAX_GROUPS
 #define FRG_DENSIFY_MAX_GROUPS 8

@@ -694,6 +694,59 @@ int frg_densify_apply(int P, int P_out, const int* plan, int n_groups, const int
  * segment of the parameter and moment buffers, P elements each. */
 int frg_reset_opacity(int P, float* raw_opacities, float* exp_avg, float* exp_avg_sq, void* hip_stream);
 
+/* ---- density / SDF field of SuGaR over K neighbour Gaussians (forward + backward) ----------------------
+ * frosting_scene/sugar_model.py: get_field_values (:1278), get_beta (:1203), compute_density (:1376), which every regularised
+ * iteration of the coarse trainers calls on up to 1 000 000 samples x 16 neighbours.  idx [N,K] (int64 as frg_knn_points
+ * writes it, or int32; 1 <= K <= FRG_KNN_MAX_K) names the Gaussians of every sample x [N,3]; points [P,3], scaling [P,3],
+ * quaternions [P,4] (real part first, used as given: pytorch3d's quaternion_to_matrix), strengths [P]; all float32,
+ * contiguous, quaternion rows 16-byte aligned.  Per pair, with A_j = R(q_j) diag(1 / max(s_j, 1e-8)):
+ *     w = A_j^T (x_s - mu_j),   o_sk = density_factor * strength_j * exp(-0.5 * clamp(w.w, 0, 1e8)).
+ * Forward outputs, each optional (NULL = not wanted, neither computed for storing nor written):
+ *     density [N] = sum_k o_sk (before the normalisation below), opacities [N,K] = o_sk,
+ *     beta [N]: FRG_FIELD_BETA_AVERAGE mean_k min(s_j); FRG_FIELD_BETA_WEIGHTED sum_k min(s_j) o_sk / max(sum_k o_sk,
+ *       opacity_min_clamp), and *beta_fallback (DEVICE memory, one float) where sum_k o_sk == 0,
+ *     sdf [N] = beta (sqrt(-2 log max(d_n, opacity_min_clamp)) - sqrt(-2 log min(density_threshold, 1))), d_n = density, rows
+ *       >= 1 replaced by d / (d.detach() + 1e-12) -- 1 in float32, with the derivative 1 / (d + 1e-12).
+ * beta and sdf need a beta_mode other than FRG_FIELD_BETA_NONE.
+ * frg_field_backward takes the same record with the upstream gradients dL_ddensity [N], dL_dopacities [N,K], dL_dbeta [N],
+ * dL_dsdf [N] (each optional, NULL = zero) and writes EVERY row of dL_dx [N,3], dL_dpoints [P,3], dL_dscaling [P,3] (zero
+ * where the 1e-8 clamp is active; beta's part goes to the first smallest component), dL_dquaternions [P,4] (w.r.t. the
+ * quaternion as given) and dL_dstrengths [P] exactly once, zeros for a Gaussian no pair names: no float atomics, the same
+ * bits on every run.  Autograd's gradient of the reference's expression, except on rows with density >= 1 when dL_dsdf is
+ * given: sqrt is taken at exactly 0 there and the reference's gradient is not finite; here the sdf's density term gets no
+ * gradient on those rows (its beta term does).
+ * An idx entry outside [0, P) is never dereferenced: the pair contributes nothing (o = 0, min scale 0) and *bad_index
+ * (DEVICE memory, one int32 the caller zeroed) is set to 1; the caller reads it to reject the call's results.
+ * workspace: 256-byte aligned, frg_field_workspace_bytes(P, N, K, flags) with FRG_FIELD_BACKWARD in flags for the backward.
+ * flags of the record: FRG_FIELD_RECOMPUTE = the pair kernel rebuilds A from the four arrays instead of reading the packed
+ * 64-byte records (a timing switch; same formulas).  N * K and 32 N must stay below 2^31. */
+#define FRG_FIELD_BETA_NONE 0
+#define FRG_FIELD_BETA_AVERAGE 1
+#define FRG_FIELD_BETA_WEIGHTED 2
+#define FRG_FIELD_BACKWARD 1
+#define FRG_FIELD_RECOMPUTE 2
+typedef struct frg_field_args {
+    size_t struct_size;
+    int P, N, K;
+    int idx_is_int64;
+    const void* idx;
+    const float *x, *points, *scaling, *quaternions, *strengths;
+    int beta_mode;
+    int flags;
+    double density_threshold, density_factor, opacity_min_clamp;
+    const float* beta_fallback;
+    float *density, *opacities, *beta, *sdf;
+    const float *dL_ddensity, *dL_dopacities, *dL_dbeta, *dL_dsdf;
+    float *dL_dx, *dL_dpoints, *dL_dscaling, *dL_dquaternions, *dL_dstrengths;
+    int* bad_index;
+    char* workspace;
+    size_t workspace_bytes;
+    void* hip_stream;
+} frg_field_args;
+size_t frg_field_workspace_bytes(int P, int N, int K, int flags);
+int frg_field_forward(const frg_field_args* args);
+int frg_field_backward(const frg_field_args* args);
+
 #ifdef __cplusplus
 }
 #endif
