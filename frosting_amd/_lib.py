@@ -182,6 +182,26 @@ class FieldArgs(C.Structure):
                 ("hip_stream", C.c_void_p)]
 
 
+class LevelsetArgs(C.Structure):
+    """frg_levelset_args (include/frosting_rasterizer.h)."""
+    _fields_ = [("struct_size", C.c_size_t),
+                ("P", C.c_int), ("R", C.c_int), ("K", C.c_int), ("n", C.c_int), ("L", C.c_int),
+                ("idx_is_int64", C.c_int),
+                ("inner_mode", C.c_int),
+                ("idx", C.c_void_p),
+                ("origins", C.c_void_p), ("directions", C.c_void_p), ("t_scale", C.c_void_p), ("t_offset", C.c_void_p), ("lin", C.c_void_p),
+                ("points", C.c_void_p), ("scaling", C.c_void_p), ("quaternions", C.c_void_p), ("strengths", C.c_void_p),
+                ("levels", C.c_double * 8),
+                ("density_factor", C.c_double),
+                ("densities", C.c_void_p), ("t_outer", C.c_void_p), ("t_inner", C.c_void_p),
+                ("first_above", C.c_void_p), ("last_above", C.c_void_p),
+                ("under_first", C.c_void_p),
+                ("normals", C.c_void_p),
+                ("bad_index", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("hip_stream", C.c_void_p)]
+
+
 # The parameters of the reference-shaped entry points are fields of the structs: their positional order, written once.
 # (argtypes of the functions and the arguments of a call are both derived from it.)
 FORWARD_POSITIONAL = [name for name, _ in ForwardArgs._fields_[1:ForwardArgs._fields_.index(("hip_stream", C.c_void_p)) + 1]]
@@ -413,6 +433,11 @@ def lib():
         L.frg_field_forward.argtypes = [C.POINTER(FieldArgs)]
         L.frg_field_backward.restype = i
         L.frg_field_backward.argtypes = [C.POINTER(FieldArgs)]
+    if hasattr(L, "frg_levelset"):
+        L.frg_levelset_workspace_bytes.restype = sz
+        L.frg_levelset_workspace_bytes.argtypes = [i, i, i, i]
+        L.frg_levelset.restype = i
+        L.frg_levelset.argtypes = [C.POINTER(LevelsetArgs)]
     _lib = L
     return L
 
@@ -469,4 +494,5 @@ EXPORTED_SYMBOLS = [
     "frg_sum_packet_bytes_ex", "frg_pack_sum_rows_ex", "frg_densify_accumulate_views",
     "frg_knn_points_workspace_bytes", "frg_knn_points",
     "frg_field_workspace_bytes", "frg_field_forward", "frg_field_backward",
+    "frg_levelset_workspace_bytes", "frg_levelset",
 ]

@@ -552,4 +552,45 @@ static int field_call(const frg_field_args* a, bool backward)
 int frg_field_forward(const frg_field_args* a) { return field_call(a, false); }
 int frg_field_backward(const frg_field_args* a) { return field_call(a, true); }
 
+// ---- level crossings of the density field along rays (levelset.hip) ----
+size_t frg_levelset_workspace_bytes(int P, int R, int K, int flags)
+{
+    (void)flags;
+    if (P <= 0 || R <= 0 || K < 1 || K > FRG_KNN_MAX_K) return 0;
+    return frg::levelset_workspace_bytes(P);
+}
+
+int frg_levelset(const frg_levelset_args* a)
+{
+    const char* what = "frg_levelset";
+    if (!a || a->struct_size != sizeof(frg_levelset_args))
+        return fail(FRG_EINVAL, "frg_levelset_args: struct_size %zu, this library expects %zu", a ? a->struct_size : (size_t)0, sizeof(frg_levelset_args));
+    if (a->K < 1 || a->K > FRG_KNN_MAX_K) return fail(FRG_EINVAL, "%s: K = %d outside 1 ... %d", what, a->K, FRG_KNN_MAX_K);
+    if (a->n < 2 || a->n > FRG_LEVELSET_MAX_SAMPLES) return fail(FRG_EINVAL, "%s: n = %d samples outside 2 ... %d", what, a->n, FRG_LEVELSET_MAX_SAMPLES);
+    if (a->L < 1 || a->L > FRG_LEVELSET_MAX_LEVELS) return fail(FRG_EINVAL, "%s: L = %d levels outside 1 ... %d", what, a->L, FRG_LEVELSET_MAX_LEVELS);
+    if (a->inner_mode != FRG_LEVELSET_INNER_LAST && a->inner_mode != FRG_LEVELSET_INNER_SECOND_CROSSING)
+        return fail(FRG_EINVAL, "%s: unknown inner_mode %d", what, a->inner_mode);
+    if (a->P < 0 || a->R < 0) return fail(FRG_EINVAL, "%s: P = %d or R = %d < 0", what, a->P, a->R);
+    if ((long long)a->R * (a->n > a->K ? a->n : a->K) > 0x7fffffffLL)
+        return fail(FRG_EINVAL, "%s: R = %d: R * max(n, K) must stay below 2^31", what, a->R);
+    if (a->R == 0) return FRG_OK;
+    if (a->P == 0) return fail(FRG_EINVAL, "%s: rays without Gaussians", what);
+    if (!a->idx || !a->origins || !a->directions || !a->t_scale || !a->t_offset || !a->lin || !a->bad_index)
+        return fail(FRG_EINVAL, "%s: null pointer (idx, origins, directions, t_scale, t_offset, lin, bad_index)", what);
+    if (!a->points || !a->scaling || !a->quaternions || !a->strengths) return fail(FRG_EINVAL, "%s: null pointer (points, scaling, quaternions, strengths)", what);
+    if (reinterpret_cast<uintptr_t>(a->quaternions) % 16 != 0) return fail(FRG_EINVAL, "%s: quaternions must be 16-byte aligned", what);
+    const size_t need = frg::levelset_workspace_bytes(a->P);
+    if (!a->workspace || a->workspace_bytes < need) return fail(FRG_EINVAL, "%s: workspace too small: need %zu bytes", what, need);
+    if (reinterpret_cast<uintptr_t>(a->workspace) % 256 != 0) return fail(FRG_EINVAL, "%s: workspace must be 256-byte aligned", what);
+    frg::LevelsetLaunch p{};
+    p.P = a->P; p.R = a->R; p.K = a->K; p.n = a->n; p.L = a->L; p.idx64 = a->idx_is_int64 ? 1 : 0; p.inner_mode = a->inner_mode;
+    p.idx = a->idx; p.origins = a->origins; p.directions = a->directions; p.t_scale = a->t_scale; p.t_offset = a->t_offset; p.lin = a->lin;
+    for (int l = 0; l < a->L; l++) p.levels[l] = (float)a->levels[l];
+    p.density_factor = (float)a->density_factor;
+    p.densities = a->densities; p.t_outer = a->t_outer; p.t_inner = a->t_inner; p.first_above = a->first_above;
+    p.last_above = a->last_above; p.under_first = a->under_first; p.normals = a->normals; p.bad_index = a->bad_index;
+    FRG_HIP(frg::launch_levelset(p, a->points, a->scaling, a->quaternions, a->strengths, a->workspace, (hipStream_t)a->hip_stream));
+    return FRG_OK;
+}
+
 }  // extern "C"

@@ -230,6 +230,30 @@ struct FieldLaunch {
 };
 size_t field_workspace_bytes(int P, int N, int K, bool backward);
 hipError_t launch_field(FieldLaunch p, bool backward, char* workspace, hipStream_t s);
+// the pack pre-pass alone: one 64-byte record per Gaussian (field_record.h) into rec [P * 4]
+hipError_t launch_field_pack(int P, const float* points, const float* scaling, const float* quaternions, const float* strengths,
+                             float4* rec, hipStream_t s);
+
+// level crossings of that field along rays (levelset.hip).  The records are field.hip's, packed into the workspace per call.
+#ifndef FRG_LEVELSET_MAX_LEVELS
+#define FRG_LEVELSET_MAX_LEVELS 8
+#endif
+struct LevelsetLaunch {
+    int P, R, K, n, L, idx64, inner_mode;
+    const void* idx;
+    const float *origins, *directions, *t_scale, *t_offset, *lin;
+    float levels[FRG_LEVELSET_MAX_LEVELS];                      // the reference's Python floats, rounded to float32 once
+    float density_factor;
+    float *densities, *t_outer, *t_inner;
+    int *first_above, *last_above;
+    unsigned char* under_first;
+    float* normals;
+    int* bad_index;
+    const float4* rec;
+};
+size_t levelset_workspace_bytes(int P);
+hipError_t launch_levelset(LevelsetLaunch p, const float* points, const float* scaling, const float* quaternions,
+                           const float* strengths, char* workspace, hipStream_t s);
 
 // adaptive density control over the flat parameter layout (densify.hip)
 #ifndef FRG_DENSIFY_MAX_GROUPS

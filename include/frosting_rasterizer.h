@@ -747,6 +747,58 @@ size_t frg_field_workspace_bytes(int P, int N, int K, int flags);
 int frg_field_forward(const frg_field_args* args);
 int frg_field_backward(const frg_field_args* args);
 
+/* ---- level-set crossings of that density field along rays (forward only) --------------------------------
+ * frosting_scene/frosting_model.py: compute_level_points_along_normals (:2016-2208, the thickness of a Frosting shell at
+ * every vertex) and compute_level_surface_points_and_range_from_camera (:1747-2013, the surface points of one camera);
+ * sugar_model.py:1885 is the latter without the inner point.  All of them run under torch.no_grad().
+ * Per ray r: origins [R,3], directions [R,3] (used as given), t_scale [R], t_offset [R], idx [R,K] (int64 or int32,
+ * 1 <= K <= FRG_KNN_MAX_K) into points [P,3], scaling [P,3], quaternions [P,4] (16-byte aligned rows), strengths [P]; per call
+ * lin [n] (DEVICE memory, 2 <= n <= FRG_LEVELSET_MAX_SAMPLES), levels[0 .. L) (in the record, 1 <= L <=
+ * FRG_LEVELSET_MAX_LEVELS; rounded to float32 once, as a Python float meeting a float32 tensor is).  All float32, contiguous.
+ *     t_j = lin[j] * t_scale[r] + t_offset[r],  x_j = o_r + t_j * d_r      (each product and sum rounded on its own: :2080-2081,
+ *                                                                           :1877-1879)
+ *     dens[r][j] = sum_k density_factor * strength * exp(-0.5 * clamp(|A^T (x_j - mu)|^2, 0, 1e8)),  A = R(q) diag(1 / max(s,
+ *       1e-8)); a value >= 1 is replaced by d / (d + 1e-12) (:2106-2111, :1900-1909)
+ * Per level (:2117-2160, :1919-1963), "above" being dens > level and "under" dens < level (equality is neither):
+ *     first_above = the first j above, 0 if none (so 0 doubles as "none");
+ *     last_above  = FRG_LEVELSET_INNER_LAST: the last j above, n - 1 if none;  FRG_LEVELSET_INNER_SECOND_CROSSING: the first j
+ *                   with j above and j + 1 under, where 0 -- no such j, or j = 0 -- becomes n - 1;
+ *     t_outer = first_above > 0 ? (level - v0) / (v1 - v0) * (t1 - t0) + t0 over samples first_above - 1, first_above : t_0;
+ *     t_inner = last_above < n - 1 ? the same form over samples last_above, last_above + 1 : t_{n-1};
+ *     under_first = dens[r][0] < level;
+ *     normals = -normalize(sum_k o_k A (A^T (p - mu)), eps 1e-12) at p = o + t_outer d (:1988-2008), written where
+ *               first_above > 0 and as zeros elsewhere.
+ * Outputs, each optional (NULL = not wanted, not written): densities [R,n]; t_outer, t_inner [L,R]; first_above, last_above
+ * [L,R] int32; under_first [L,R] uint8; normals [L,R,3].
+ * An idx entry outside [0, P) is never dereferenced: the pair contributes nothing and *bad_index (DEVICE memory, one int32
+ * the caller zeroed) is set to 1.  workspace: 256-byte aligned, frg_levelset_workspace_bytes(P, R, K, 0) bytes (the packed
+ * records of frg_field_forward).  R * max(n, K) must stay below 2^31; R == 0 succeeds and launches nothing. */
+#define FRG_LEVELSET_MAX_SAMPLES 32
+#define FRG_LEVELSET_MAX_LEVELS 8
+#define FRG_LEVELSET_INNER_LAST 0
+#define FRG_LEVELSET_INNER_SECOND_CROSSING 1
+typedef struct frg_levelset_args {
+    size_t struct_size;
+    int P, R, K, n, L;
+    int idx_is_int64;
+    int inner_mode;
+    const void* idx;
+    const float *origins, *directions, *t_scale, *t_offset, *lin;
+    const float *points, *scaling, *quaternions, *strengths;
+    double levels[FRG_LEVELSET_MAX_LEVELS];
+    double density_factor;
+    float *densities, *t_outer, *t_inner;
+    int *first_above, *last_above;
+    unsigned char* under_first;
+    float* normals;
+    int* bad_index;
+    char* workspace;
+    size_t workspace_bytes;
+    void* hip_stream;
+} frg_levelset_args;
+size_t frg_levelset_workspace_bytes(int P, int R, int K, int flags);
+int frg_levelset(const frg_levelset_args* args);
+
 #ifdef __cplusplus
 }
 #endif
